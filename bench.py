@@ -14,6 +14,15 @@ per horizon (HumanoidPPO.yaml:66, 32 steps), asynchronously while the next horiz
 timed window starts a fresh horizon and ends by gathering any partial one, so every window
 holds at least one complete gather whatever --steps is.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and
+prints the line: the headline figure, `ms_per_step` and the `roofline` of the kernel timed inside
+that same window. Everything that takes runs of its own is behind `--full`: the HIP-graph replay of
+the same steps, the Cartpole / Ant side configs, the obs/reward-fuse roofline, INTEGRATION path (A),
+the CPU baselines and, at N>1, the no-gather window and the stand-alone gather (`--no-side`,
+`--no-cpu-baseline`, `--fuse-envs 0` drop single legs of a full run). `--dump-outputs DIR` writes what
+the last timed step returned (obs, rew, resets of this rank's shard) as DIR/<name>.npy, float32;
+with the same arguments the seeded inputs, and so these arrays, are the same from run to run.
+
 Prints ONE JSON line (rank 0). `roofline` is for the dominant kernel — the launch the fused
 step runs, named in the line (Humanoid / Ant: k_env_step_pair<Tgs<TopoCT<Robot*>>> under the
 reference's TGS solver, k_env_step_pair<TopoCT<Robot*>> under PGS, two envs per wavefront;
@@ -61,6 +70,11 @@ def parse(argv=None):
                     help="diagnostic: time the window without kernel events, events in a second window")
     ap.add_argument("--fuse-envs", type=int, default=1048576,
                     help="envs of the obs/reward-fuse HBM roofline side measurement (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (graph replay, side configs, obs/reward fuse, "
+                         "path (A), CPU baselines; N>1: no-gather window, stand-alone gather)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (obs, rew, resets) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -92,6 +106,7 @@ class ShardLoop:
         self.h = 0          # next row of the current horizon
         self.gathering = True
         self.ev = None      # (starts, ends, every, k0): kernel events on steps k0, k0 + every, ...
+        self.last = None    # what the env's last step returned: ({"obs", "states"}, rew, resets, extras)
 
     def step(self, k: int):
         a = self.actions[k % len(self.actions)]
@@ -99,11 +114,13 @@ class ShardLoop:
             self.env.kernel_events = self.ev[:2] if (k - self.ev[3]) % self.ev[2] == 0 else None
         r = self.rollout
         if r is None:
-            return self.env.step(a)[0]
+            self.last = self.env.step(a)
+            return self.last[0]
         if self.env.fused:
-            obs = self.env.step(a, out=r.slot(self.h))[0]
+            self.last = self.env.step(a, out=r.slot(self.h))
+            obs = self.last[0]
         else:
-            obs, rew, done, _ = self.env.step(a)
+            obs, rew, done, _ = self.last = self.env.step(a)
             r.record(self.h, obs["obs"], rew, done)
         self.h += 1
         if self.h == self.H:
@@ -321,6 +338,32 @@ def action_pool(view, n, A, seed, device, pool=16):
     return actions
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: upper bound on what one run writes, all ranks together
+
+
+def last_outputs(loop) -> dict:
+    """Host float32 copies of what the loop's last step returned to its caller."""
+    import torch
+    obs, rew, resets = loop.last[0]["obs"], loop.last[1], loop.last[2]
+    return {k: v.detach().to("cpu", torch.float32).numpy()
+            for k, v in (("obs", obs), ("rew", rew), ("resets", resets))}
+
+
+def dump_outputs(dirpath: str, arrays: dict, seed: int, rank: int = 0, world: int = 1) -> None:
+    """Write `arrays` (each [envs, ...]) as dirpath/<name>.npy (rank r > 0: <name>_rank<r>.npy).
+    Past this rank's share of DUMP_BYTES the same seeded sample of env rows, in ascending order, is
+    written of every array."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(1, n)
+    keep = (DUMP_BYTES // world) // max(1, row_bytes)
+    rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False)) if keep < n else None
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a if rows is None else a[rows], dtype=np.float32)
+        np.save(os.path.join(dirpath, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def solver_overrides(solver: str) -> list:
     return {"config": [], "tgs": ["solver_type=1"], "pgs": ["solver_type=0"]}[solver]
 
@@ -437,6 +480,7 @@ def main():
         # diagnostic: the same window plain, with torch events around every launch, and with
         # the dispatch-carried events
         win = loop.window(args.warmup, args.steps, sync, barrier)
+        dumped = last_outputs(loop) if args.dump_outputs else None
         s_all = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
         e_all = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
         env._ev_i = 0
@@ -464,6 +508,7 @@ def main():
         if env.fused:
             NL.check(NL.lib().mi_sim_time_launches(view.handle, TIME_EVERY, args.steps), "mi_sim_time_launches")
         win = loop.window(args.warmup, args.steps, sync, barrier)
+        dumped = last_outputs(loop) if args.dump_outputs else None
     elapsed = win["elapsed"]
     kernel_ms = launch_times_ms(view, args.steps) if env.fused else None
     gather_info = None
@@ -471,25 +516,28 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        # the same window without gathers (exposed gather time = difference), and one
-        # synchronous horizon gather on its own
-        nog = loop.window(args.warmup + args.steps, args.steps, sync, barrier, gathering=False)
-        t = torch.tensor([nog["elapsed"]], device=device, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        nog_el = float(t.item())
-        sync(); barrier(); sync()
-        t0 = time.perf_counter()
-        rollout.gather(async_op=False)
-        sync(); barrier(); sync()
-        g_ms = (time.perf_counter() - t0) * 1e3
         gather_info = {"collective": "gather to rank 0 (learner), RCCL" if dist.get_backend() == "nccl"
                        else f"gather to rank 0, {dist.get_backend()}",
                        "horizon": loop.H, "gathers_in_window": win["gathers"],
                        "gather_bytes_per_rank": win["bytes"] // max(1, win["gathers"]),
-                       "bytes_per_rank_in_window": win["bytes"],
-                       "window_ms_no_gather": round(nog_el * 1e3, 3),
-                       "exposed_gather_ms": round((elapsed - nog_el) * 1e3, 3),
-                       "standalone_horizon_gather_ms": round(g_ms, 3)}
+                       "bytes_per_rank_in_window": win["bytes"]}
+        if args.full:
+            # the same window without gathers (exposed gather time = difference), and one
+            # synchronous horizon gather on its own
+            nog = loop.window(args.warmup + args.steps, args.steps, sync, barrier, gathering=False)
+            t = torch.tensor([nog["elapsed"]], device=device, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            nog_el = float(t.item())
+            sync(); barrier(); sync()
+            t0 = time.perf_counter()
+            rollout.gather(async_op=False)
+            sync(); barrier(); sync()
+            g_ms = (time.perf_counter() - t0) * 1e3
+            gather_info.update({"window_ms_no_gather": round(nog_el * 1e3, 3),
+                                "exposed_gather_ms": round((elapsed - nog_el) * 1e3, 3),
+                                "standalone_horizon_gather_ms": round(g_ms, 3)})
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped, args.seed, rank, world)
     total_env_steps = world * n_local * args.steps
     value = total_env_steps / elapsed
     nan = view.nan_count()
@@ -534,7 +582,7 @@ def main():
         }
         if gather_info:
             out["rollout_gather"] = gather_info
-    if not distributed and env.fused:
+    if args.full and not distributed and env.fused:
         # the same workload replayed from a captured HIP graph (16 steps per graph, as the PPO
         # rollout runs it): what the step costs without per-step Python / launch overhead
         G = len(actions)
@@ -557,7 +605,9 @@ def main():
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(out), flush=True)
+    elif rank == 0:
         if world == 1 and not args.no_side and args.task == "Humanoid":
             out["side_configs"] = [side_run("Cartpole", 4096, solver=args.solver),
                                    side_run("Ant", 4096, solver=args.solver)]

@@ -30,6 +30,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+LOGS=$_   # the log folder made above (bash: last argument of the previous command)
 TASK=${TASK:-Humanoid}
 TAG=${TAG:-cur}
 RP="rocprofv3 --output-format csv"
@@ -64,9 +65,9 @@ recipe() {
   smoke)
     run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
   bench)
-    run bench_default 600 python -u bench.py ;;
+    run bench_default 600 python -u bench.py --full ;;
   prof)
-    run prof_bench 600 $RP --kernel-trace --stats -d gpurun_out/prof_bench -o run -- python3 bench.py ;;
+    run prof_bench 600 $RP --kernel-trace --stats -d "$LOGS/prof_bench" -o run -- python3 bench.py --full ;;
   fuse)
     run fuse_h 300 python -u tools/fuse_roofline.py Humanoid 4096,65536,131072,262144,1048576,2097152
     run fuse_a 300 python -u tools/fuse_roofline.py Ant 4096,65536,131072,262144,1048576,2097152
