@@ -308,6 +308,66 @@ int mi_dr_apply_observations(mi_sim* sim, float* obs /*[N,O]*/, const int64_t* r
 /* Per-env DR schedule state -> host [N,6] uint32: obs (counter, epoch, draws), act (same). */
 int mi_get_dr_state(mi_sim* sim, uint32_t* out /*[N,6] host*/);
 
+/* --- per-env physics parameters + physics DR (randomize.py:308-430) -----------------------
+ * The `simulation`, `articulation_views` and `rigid_prim_views` groups of
+ * `domain_randomization.randomization_params` (docs/domain_randomization.md:147-167), which the
+ * reference hands to omni.replicator.isaac.physics_view. An mi_sim has an OPTIONAL device table
+ * with one record per env, a whole number of 128-byte lines:
+ *     gravity[3], friction, damping[D], armature[D], padding
+ * Absent (the default), every kernel is the same code as without this feature and reads the
+ * sim-wide mi_sim_params / mi_model_desc values. The first mi_set_env_params or
+ * mi_sim_set_phys_dr allocates it (filled with the nominal values) and from then on mi_sim_step,
+ * mi_env_step and the task path launch kernel variants that read gravity, ground / self-contact
+ * friction, joint damping and armature from the record of the env they simulate. Covered: the
+ * two-envs-per-wavefront kernels (both solvers) and the one-lane-per-env kernels (incl. the
+ * analytic cart-pole, which takes gravity and damping = (cart, pole); armature and friction are
+ * MI_E_ARG there). The wavefront-per-env path (MI_WAVE_PAIR=0, runtime tables) refuses the table
+ * with MI_E_STATE. */
+enum { MI_ENVP_GRAVITY = 0,   /* dim 3: SimulationContext gravity (randomize.py:308-342)        */
+       MI_ENVP_FRICTION = 1,  /* dim 1: material_properties' dynamic friction (:344-430)        */
+       MI_ENVP_DAMPING = 2,   /* dim D: ArticulationView.set_gains kds / `damping`              */
+       MI_ENVP_ARMATURE = 3   /* dim D: ArticulationView.set_armatures / `joint_armatures`      */ };
+/* ArticulationView-style indexed setter / getter of one attribute (stream-ordered, no host
+ * block once the table exists). idx NULL: rows 0..n-1; out-of-range ids are ignored. */
+int mi_set_env_params(mi_sim* sim, int32_t attr, const float* values /*[n,dim] device*/,
+                      const int64_t* idx /*[n] device|NULL*/, int32_t n, void* stream);
+/* Before the table exists: the nominal values broadcast over the envs. */
+int mi_get_env_params(mi_sim* sim, int32_t attr, float* out /*[N,dim] device*/, void* stream);
+/* Drops the table (and leaves the physics DR schedules off): back to the nominal physics and to
+ * the kernels that know no table. Waits for the device. */
+int mi_sim_clear_env_params(mi_sim* sim);
+
+/* Physics DR schedules (include/mi_dr_phys.h): per attribute an optional on_reset and an optional
+ * on_interval schedule (randomize.py:313-342,393-428). */
+enum { MI_DR_OP_DIRECT = 2 };   /* docs/domain_randomization.md:85-89 */
+typedef struct mi_dr_phys_sched {
+    int32_t enabled;            /* 0: schedule absent                                  */
+    int32_t operation;          /* MI_DR_OP_* incl. MI_DR_OP_DIRECT                    */
+    int32_t distribution;       /* MI_DR_DIST_*                                        */
+    int32_t frequency_interval; /* on_interval only; all on_interval schedules of one  */
+                                /* sim share one value (one interval counter per env)  */
+    const float* p0;            /* host [dim]: mean | lower, per component             */
+    const float* p1;            /* host [dim]: std | upper                             */
+} mi_dr_phys_sched;
+typedef struct mi_dr_phys_params {
+    mi_dr_phys_sched on_reset[4], on_interval[4];   /* indexed by MI_ENVP_*            */
+    int32_t min_frequency;      /* docs/domain_randomization.md:120-128                */
+} mi_dr_phys_params;
+/* Randomizer.set_up_domain_randomization's physics groups (randomize.py:85-110). The first call
+ * that turns a schedule on allocates the table and zeroes the per-env schedule state; later
+ * calls (set_dr_distribution_parameters, randomize.py:461-488) replace the schedules and keep
+ * that state. NULL (or nothing enabled) turns the schedules off; the table stays. A configuration
+ * call: waits for the device before it replaces the schedules (not inside a stream capture). */
+int mi_sim_set_phys_dr(mi_sim* sim, const mi_dr_phys_params* dr /*host|NULL*/);
+/* dr.physics_view.step_randomization(reset_inds) (docs/domain_randomization.md:251-260,
+ * in_hand_manipulation.py:226,271-275) as a mask: one launch, no allocation, no host sync
+ * (capturable). mi_env_step issues it itself, before its fused launch, with the incoming
+ * reset_buf; the method-by-method path calls it before mi_task_pre_step consumes the mask.
+ * A no-op while no schedule is on. */
+int mi_dr_phys_step(mi_sim* sim, const int64_t* reset_buf /*[N] device*/, void* stream);
+/* Per-env schedule state -> host [N,4] uint32: since, counter, epoch, draws (zeros while off). */
+int mi_get_phys_dr_state(mi_sim* sim, uint32_t* out /*[N,4] host*/);
+
 /* --- utilities --------------------------------------------------------------------- */
 /* U(lo,hi) Philox4x32-10 actions for the random-policy driver (scripts/random_policy.py:57),
  * keyed on (seed, env_id_offset + env, step). */

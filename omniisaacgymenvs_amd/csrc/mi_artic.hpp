@@ -107,7 +107,12 @@ MI_D void make_row(const DevModel& m, const WS& w, int r, int l, const float* f)
     }
 }
 
-MI_D void artic_substep(const DevModel& m, const DevState& st, const SimP& p, int i) {
+// kEnvP: joint damping / armature from env i's record ep of the per-env parameter table
+// (include/mi_sim.h mi_set_env_params; layout: mi_topo.hpp); the caller passes the record's
+// gravity and friction in p.
+template <bool kEnvP = false>
+MI_D void artic_substep(const DevModel& m, const DevState& st, const SimP& p, int i,
+                        const float* ep = nullptr) {
     const int N = st.N, L = m.L, D = m.D, nv = m.nv, nr = m.nr;
     const float dt = p.dt;
     WS w(st.ws, m.slots, i);
@@ -257,8 +262,14 @@ MI_D void artic_substep(const DevModel& m, const DevState& st, const SimP& p, in
         const float Ck = dot6(s, F);
         float rhs = -Ck;
         if (k >= nr) {
-            diag += m.armature[l] + dt * m.damping[l];
-            rhs += st.eff[sx(st, k - nr, i)] - m.damping[l] * w[m.o_u + k];
+            if constexpr (kEnvP) {
+                const float damp = ep[4 + l - 1], arm = ep[4 + D + l - 1];
+                diag += arm + dt * damp;
+                rhs += st.eff[sx(st, k - nr, i)] - damp * w[m.o_u + k];
+            } else {
+                diag += m.armature[l] + dt * m.damping[l];
+                rhs += st.eff[sx(st, k - nr, i)] - m.damping[l] * w[m.o_u + k];
+            }
         }
         w[m.o_M + k * nv + k] = diag;
         w[m.o_r + k] = rhs;

@@ -355,7 +355,12 @@ MI_D void pair_wcol_w(const WSrc& ws, int g0, int kc, int nv, float (&wq)[4]) {
 template <class TP>
 MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevState& st,
                              const SimP& p, int i, int wv_, const float* mcb, float* sm, float* gW,
-                             bool load_state, bool store_state, int& prio, int& load) {
+                             bool load_state, bool store_state, int& prio, int& load,
+                             const float* ep = nullptr) {
+    // ep (TP::kEnvP only): env i's record of the per-env parameter table. LDS and registers are
+    // both full here (Humanoid: 432 B of LDS spare per workgroup, 2 waves / SIMD), so the record
+    // is not kept across the substep: its lines are read where the state's effort line is (P3:
+    // lane = DOF, coalesced), gravity at P1 and friction once ahead of the PGS sweeps
     static_assert(TP::kCT && TP::nv <= 32, "paired kernel: compiled topology, nv <= 32");
     const int lane = pair_l64() & 31;
     const int N = st.N, L = m.L, D = m.D, nv = m.nv, nr = m.nr;
@@ -386,7 +391,7 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
     // ---- P1: local transforms, then chain walks + link inertia / Newton-Euler (lane = link)
     for (int l = 1 + lane; l < L; l += 32) wave_link_local(mc, t, sm, l);
     wave_sync();
-    for (int l = lane; l < L; l += 32) wave_link_forward(mc, nr, t, sm, l, p);
+    for (int l = lane; l < L; l += 32) wave_link_forward<TP::kEnvP>(mc, nr, t, sm, l, p, ep);
     wave_sync();
     STAMP(1);
     // ---- P2: composite inertia / force
@@ -427,8 +432,15 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
         float diag = dot6(s, f);
         float r = -dot6(s, F);
         if (k >= nr) {
-            const float damp = mc.lf(MC_DAMP, l);
-            diag += mc.lf(MC_ARM, l) + dt * damp;
+            float damp, arm;
+            if constexpr (TP::kEnvP) {
+                damp = ep[kEnvpDamping + k - nr];
+                arm = ep[kEnvpDamping + D + k - nr];
+            } else {
+                damp = mc.lf(MC_DAMP, l);
+                arm = mc.lf(MC_ARM, l);
+            }
+            diag += arm + dt * damp;
             r += st.eff[sx(st, k - nr, i)] - damp * us[k];
         }
         rhs[k] = r;
@@ -777,7 +789,9 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
     load = max(load, nrows);   // half-uniform: this env's constraint rows (contact + limit; A/B
                                // round 5: 0.1166 ms vs 0.1178 ranking by contact rows alone)
     const int nrows_max = pmax(nrows);
-    const float mu = p.friction;
+    float mu;
+    if constexpr (TP::kEnvP) mu = ep[kEnvpFriction];
+    else mu = p.friction;
     if (nrows_max <= TP::kLamRows) {
         // Delassus space: lane r holds row r's v_r = J_r . u and A[r][s] = J_r . W_s (J_r rebuilt
         // here from the contact data: no J rows in LDS; W rows past the LDS ones from the slab).
@@ -945,6 +959,9 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
             const int nrh = __builtin_amdgcn_readlane(nrows, 32 * h);
             const int nnh = 3 * __builtin_amdgcn_readlane(ncon, 32 * h);
             float* smh = sm + (h - me) * t.env_stride;                 // env of half h
+            float muh = mu;                                            // its friction (all 64 lanes)
+            if constexpr (TP::kEnvP)
+                muh = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mu), 32 * h));
             if (nrh == 0) {
                 // no rows: u = u*; TGS integrates positions with u-bar = u* as well
                 if constexpr (TP::kTgs) {
@@ -1088,7 +1105,7 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
                 float lamn = 0.0f;
 #if MI_PAIR_SWEEP_FMA
                 const float tl = __builtin_fmaf(b, ia, lam);   // lane = row: lam changes at its own row only
-                float muv = mu, lov = 0.0f, hiv = 0.0f;        // mu in a VGPR: mu lambda_n in one v_mul
+                float muv = muh, lov = 0.0f, hiv = 0.0f;       // mu in a VGPR: mu lambda_n in one v_mul
                 asm volatile("" : "+v"(muv));
 #endif
                 // rows rr .. rr + PA - 1 of A in flight. The scratch is NOT zeroed (no memset at
@@ -1143,7 +1160,7 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
                         (void)lw;
 #else
                         const bool fric = kd == 1 || kd == 2;
-                        const float lim = mu * lamn;
+                        const float lim = muh * lamn;
                         const float mine = __builtin_amdgcn_fmed3f(lam + (b - v) * ia, fric ? -lim : 0.0f,
                                                                    fric ? lim : __builtin_huge_valf());
                         // the owner forms the lambda change itself (mine - lam there is exactly

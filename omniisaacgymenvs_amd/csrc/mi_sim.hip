@@ -96,9 +96,23 @@ struct mi_sim {
     int tev_every = 0;
     long long tev_seen = 0;
     int tev_rec = 0;
+    // per-env physics parameters (mi_set_env_params): one record per env of envp_stride floats
+    // (whole 128-B lines): gravity 3, friction, damping D, armature D. envp == nullptr (default):
+    // no table, the plain kernels run; else the EnvP / *_envp kernel variants
+    float* envp = nullptr;
+    int envp_stride = 0;
+    std::vector<float> nominal;       // the sim-wide values in record order [4 + 2 D]
+    const float* nominal_dev = nullptr;
+    // physics DR schedules (mi_sim_set_phys_dr): descriptor + per-component distribution
+    // parameters in device memory (a captured graph sees later updates), state [4][N]
+    bool pdr_on = false;
+    void* pdr_desc = nullptr;         // PhysDR
+    float* pdr_prm = nullptr;         // [4][4 + 2 D]: on_reset p0, p1, on_interval p0, p1
+    uint32_t* pdr_state = nullptr;    // [4][N]: since, counter, epoch, draws
 };
 static hipError_t timed_launch(mi_sim* s, void* stream, hipEvent_t* ev0, hipEvent_t* ev1);
 static int flush_pending(mi_sim* s, void* stream);
+static int dr_phys_step(mi_sim* s, const int64_t* reset_buf, hipStream_t stream);
 
 static int dev_alloc(mi_sim* s, void** p, size_t bytes) {
     if (bytes == 0) bytes = 16;
@@ -123,8 +137,26 @@ static inline dim3 grid_for(const mi_sim* s, int n) { return dim3((n + s->block 
 // ---------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------
+// kEnvP: gravity, friction, joint damping and armature from env i's record ep of the per-env
+// parameter table (include/mi_sim.h mi_set_env_params) instead of the sim-wide values
+template <bool kEnvP = false>
 __device__ __forceinline__ void physics_env(const DevModel& m, const DevState& st, const SimP& p,
-                                            int i, int substeps) {
+                                            int i, int substeps, const float* ep = nullptr) {
+    if constexpr (kEnvP) {
+        // the record's scalars once per launch, in registers: the substeps see them as the sim's
+        SimP pe = p;
+        pe.g[0] = ep[0]; pe.g[1] = ep[1]; pe.g[2] = ep[2];
+        pe.friction = ep[kEnvpFriction];
+        if (m.dyn == MI_DYN_CARTPOLE) {
+            DevModel me = m;
+            me.cart_damping = ep[kEnvpDamping];
+            me.pole_damping = ep[kEnvpDamping + 1];
+            physics_env<false>(me, st, pe, i, substeps);
+        } else {
+            for (int s = 0; s < substeps; ++s) artic_substep<true>(m, st, pe, i, ep);
+        }
+        return;
+    }
     if (m.dyn == MI_DYN_CARTPOLE) {
         const int N = st.N;
         float x = st.q[sx(st, 0, i)], th = st.q[sx(st, 1, i)], xd = st.qd[sx(st, 0, i)], thd = st.qd[sx(st, 1, i)];
@@ -141,6 +173,12 @@ __global__ void k_sim_step(DevModel m, DevState st, SimP p, int substeps) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= st.N) return;
     physics_env(m, st, p, i, substeps);
+}
+__global__ void k_sim_step_envp(DevModel m, DevState st, SimP p, int substeps, const float* envp,
+                                int envp_stride) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= st.N) return;
+    physics_env<true>(m, st, p, i, substeps, envp + (size_t)i * envp_stride);
 }
 
 __global__ void k_pre_step(DevModel m, DevState st, DevTask tp, const float* actions,
@@ -374,6 +412,33 @@ __global__ void k_is_done(DevState st, DevTask tp, const float* obs, int64_t* re
     reset_buf[i] = nan_guard(st, i, d);
 }
 
+// Steps 3 and 4 of the one-lane fused env step, shared as source by k_env_step and k_env_step_envp (a
+// macro, not a function: the plain kernel compiles from the very tokens it always had, so its code
+// cannot change with the per-env variant).
+#define MI_ENV_STEP_POST()                                                                          \
+    /* 3. post_physics_step into the unclamped row, then _process_data's obs clamp */               \
+    const int O = tp.O;                                                                             \
+    float* R = (obs_task ? obs_task : obs_out) + (size_t)O * i;                                     \
+    if (tp.kind == MI_TASK_CARTPOLE)                                                                \
+        cartpole_post(st, tp, i, R, rew, reset_buf, progress_buf);                                  \
+    else if (tp.dr_act)   /* task.actions = the noisy actions pre_physics_step received */          \
+        loco_post(m, st, tp, i, actions_out + (size_t)tp.A * i, INFINITY, R, rew, reset_buf,        \
+                  progress_buf, pot, prev);                                                         \
+    else                                                                                            \
+        loco_post(m, st, tp, i, actions + (size_t)tp.A * i, tp.clip_actions, R, rew, reset_buf,     \
+                  progress_buf, pot, prev);                                                         \
+    /* 4. observation noise DR on task.obs_buf with the new reset_buf (vec_env_rlgames.py:70-71) */ \
+    if (tp.dr_obs) dr_row(st, tp, 0, i, R, O, reset_buf[i] != 0);                                   \
+    const float co = tp.clip_obs;                                                                   \
+    float* OUT = obs_out + (size_t)O * i;                                                           \
+    if (obs_task) {                                                                                 \
+        for (int k = 0; k < O; ++k) OUT[k] = clampf(R[k], -co, co);                                 \
+    } else if (co < INFINITY) {                                                                     \
+        for (int k = 0; k < O; ++k) OUT[k] = clampf(OUT[k], -co, co);                               \
+    }                                                                                               \
+    if (rew_out) rew_out[i] = rew[i];                                                               \
+    if (reset_out) reset_out[i] = reset_buf[i];
+
 __global__ void k_env_step(DevModel m, DevState st, SimP p, DevTask tp, const float* actions,
                            int substeps, float* obs_out, float* obs_task, float* rew,
                            int64_t* reset_buf, int64_t* progress_buf, float* pot, float* prev,
@@ -384,28 +449,20 @@ __global__ void k_env_step(DevModel m, DevState st, SimP p, DevTask tp, const fl
     task_pre_env(m, st, tp, i, actions, reset_buf, progress_buf, pot, prev, actions_out, true);
     // 2. controlFrequencyInv x World.step
     physics_env(m, st, p, i, substeps);
-    // 3. post_physics_step into the unclamped row, then _process_data's obs clamp
-    const int O = tp.O;
-    float* R = (obs_task ? obs_task : obs_out) + (size_t)O * i;
-    if (tp.kind == MI_TASK_CARTPOLE)
-        cartpole_post(st, tp, i, R, rew, reset_buf, progress_buf);
-    else if (tp.dr_act)   // task.actions = the noisy actions pre_physics_step received
-        loco_post(m, st, tp, i, actions_out + (size_t)tp.A * i, INFINITY, R, rew, reset_buf,
-                  progress_buf, pot, prev);
-    else
-        loco_post(m, st, tp, i, actions + (size_t)tp.A * i, tp.clip_actions, R, rew, reset_buf,
-                  progress_buf, pot, prev);
-    // 4. observation noise DR on task.obs_buf with the new reset_buf (vec_env_rlgames.py:70-71)
-    if (tp.dr_obs) dr_row(st, tp, 0, i, R, O, reset_buf[i] != 0);
-    const float co = tp.clip_obs;
-    float* OUT = obs_out + (size_t)O * i;
-    if (obs_task) {
-        for (int k = 0; k < O; ++k) OUT[k] = clampf(R[k], -co, co);
-    } else if (co < INFINITY) {
-        for (int k = 0; k < O; ++k) OUT[k] = clampf(OUT[k], -co, co);
-    }
-    if (rew_out) rew_out[i] = rew[i];
-    if (reset_out) reset_out[i] = reset_buf[i];
+    MI_ENV_STEP_POST();
+}
+
+// the same step with the per-env parameter table (launched only while one exists)
+__global__ void k_env_step_envp(DevModel m, DevState st, SimP p, DevTask tp, const float* actions,
+                                int substeps, float* obs_out, float* obs_task, float* rew,
+                                int64_t* reset_buf, int64_t* progress_buf, float* pot, float* prev,
+                                float* actions_out, float* rew_out, int64_t* reset_out,
+                                const float* envp, int envp_stride) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= st.N) return;
+    task_pre_env(m, st, tp, i, actions, reset_buf, progress_buf, pot, prev, actions_out, true);
+    physics_env<true>(m, st, p, i, substeps, envp + (size_t)i * envp_stride);
+    MI_ENV_STEP_POST();
 }
 
 // ---- wavefront-per-env articulation path (one 64-lane workgroup = one env) -------------
@@ -419,6 +476,10 @@ struct KParams {
     SimP p;
     DevTask tp;
     float* rows;
+    // per-env parameter table (after every field the plain kernels read: their offsets stand);
+    // read by the EnvP instantiations only
+    const float* envp;
+    int envp_stride;
 };
 
 // launch with the model's compile-time topology (mi_topo_gen.hpp) or the runtime tables
@@ -462,6 +523,7 @@ static int sync_kparams(mi_sim* s) {
     if (!s->wave) return MI_OK;
     KParams h{};
     h.m = s->dm; h.t = s->wt; h.st = s->ds; h.p = s->sp; h.tp = s->tp; h.rows = s->rows;
+    h.envp = s->envp; h.envp_stride = s->envp_stride;
     if (!s->kp_dev) {
         void* p = nullptr;
         int rc = dev_alloc(s, &p, sizeof(KParams));
@@ -945,8 +1007,10 @@ __global__ __launch_bounds__(512) MI_PAIR_OCC void k_sim_step_pair(const KParams
     int load = 0;                          // this env's most constraint rows in a substep (unused here)
     for (int s = 0; s < substeps; ++s) {
         const KParams* k = opaque_kp(kp);
+        const float* ep = nullptr;         // env i's parameter record (the env the wave simulates,
+        if constexpr (T::kEnvP) ep = k->envp + (size_t)i * k->envp_stride;   // not its workgroup slot)
         pair_artic_substep<T>(k->m, k->t, k->st, k->p, i, pair_wave(), smem, sm, gW, s == 0, s == substeps - 1,
-                              prio, load);
+                              prio, load, ep);
     }
     // World.step() then the getters (locomotion.py:81-89): the final state is still in LDS, so the
     // launch writes the getters' row-major mirrors itself (the same values it stored to the
@@ -993,8 +1057,10 @@ __global__ __launch_bounds__(512) MI_PAIR_OCC void k_env_step_pair(const KParams
     int load = 0;                          // this env's most constraint rows in a substep
     for (int s = 0; s < substeps; ++s) {
         const KParams* k = opaque_kp(kp);
+        const float* ep = nullptr;         // env i's parameter record (the env the wave simulates,
+        if constexpr (T::kEnvP) ep = k->envp + (size_t)i * k->envp_stride;   // not its workgroup slot)
         pair_artic_substep<T>(k->m, k->t, k->st, k->p, i, pair_wave(), smem, sm, gW, s == 0, s == substeps - 1,
-                              prio, load);
+                              prio, load, ep);
     }
     STAMP_RESET();
     pair_loco_post(m, t, st, tp, i, sm, a_lane, obs_out, obs_task, rew, reset_buf, progress_buf,
@@ -1102,6 +1168,83 @@ __global__ void k_fill_uniform(int N, int64_t off, float* out, int cols, uint64_
     for (int c = 0; c < cols; ++c) {
         if ((c & 3) == 0) uniform4(seed, gid, (uint32_t)step, (uint32_t)(c >> 2), 1, u);
         out[(size_t)i * cols + c] = w * u[c & 3] + lo;
+    }
+}
+
+// ---- per-env parameter table (include/mi_sim.h mi_set_env_params) -----------------------
+// record k-th float of attribute a: base(a) + component; dims 3, 1, D, D
+static inline int envp_base(int attr, int D) { return attr == MI_ENVP_GRAVITY ? 0 : attr == MI_ENVP_FRICTION ? 3 : attr == MI_ENVP_DAMPING ? 4 : 4 + D; }
+static inline int envp_dim(int attr, int D) { return attr == MI_ENVP_GRAVITY ? 3 : attr == MI_ENVP_FRICTION ? 1 : D; }
+
+// every record <- the nominal values (one lane per float of the table, padding zeroed)
+__global__ __launch_bounds__(256) void k_envp_fill(float* __restrict__ envp, int stride, int recw,
+                                                   const float* __restrict__ nominal, int N) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)N * stride) return;
+    const int k = (int)(t % stride);
+    envp[t] = k < recw ? nominal[k] : 0.0f;
+}
+// rows of one attribute -> the records of envs idx[r] (or r); out-of-range ids are ignored
+__global__ __launch_bounds__(256) void k_envp_set(float* __restrict__ envp, int stride, int base, int dim,
+                                                  const float* __restrict__ values,
+                                                  const int64_t* __restrict__ idx, int n, int N) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)n * dim) return;
+    const int r = (int)(t / dim), c = (int)(t - (int64_t)r * dim);
+    const int64_t i = idx ? idx[r] : (int64_t)r;
+    if (i < 0 || i >= N) return;
+    envp[(size_t)i * stride + base + c] = values[t];
+}
+// one attribute of every env -> [N, dim] (envp == nullptr: the nominal values, broadcast)
+__global__ __launch_bounds__(256) void k_envp_get(const float* __restrict__ envp, int stride, int base, int dim,
+                                                  const float* __restrict__ nominal, float* __restrict__ out,
+                                                  int N) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)N * dim) return;
+    const int i = (int)(t / dim), c = (int)(t - (int64_t)i * dim);
+    out[t] = envp ? envp[(size_t)i * stride + base + c] : nominal[base + c];
+}
+
+// ---- physics DR schedule kernel (include/mi_dr_phys.h) -----------------------------------
+struct PhysDR {
+    int min_frequency, freq, any_interval, pad;
+    int r_on[4], r_op[4], r_dist[4], i_on[4], i_op[4], i_dist[4];
+};
+// step_randomization(reset mask): one lane per env. Almost every call of almost every env only
+// advances its four counters (field-major [4][N]: coalesced); an env whose schedule fired
+// recomputes the scheduled attributes of its record from (epoch, draws).
+__global__ __launch_bounds__(256) void k_dr_phys_step(int N, int64_t off, uint64_t seed, int D,
+                                                      const PhysDR* __restrict__ d,
+                                                      const float* __restrict__ prm,
+                                                      const float* __restrict__ nominal,
+                                                      uint32_t* __restrict__ ps, float* __restrict__ envp,
+                                                      int stride, const int64_t* __restrict__ reset_buf) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const size_t n = (size_t)N;
+    const mi_dr_phys_env e = mi_dr_phys_begin(ps[i], ps[n + i], ps[2 * n + i], ps[3 * n + i],
+                                              reset_buf[i] != 0, d->min_frequency, d->any_interval, d->freq);
+    ps[i] = e.since; ps[n + i] = e.counter; ps[2 * n + i] = e.epoch; ps[3 * n + i] = e.draws;
+    if (!(e.reset || e.fire)) return;
+    const uint64_t gid = (uint64_t)(off + i);
+    const int recw = 4 + 2 * D;
+    float* rec = envp + (size_t)i * stride;
+    for (int a = 0; a < MI_DR_PHYS_ATTRS; ++a) {
+        const int r_on = d->r_on[a], i_on = d->i_on[a];
+        if (!((e.reset && r_on) || (e.fire && i_on))) continue;   // only a schedule that fired rewrites
+        const int base = a == 0 ? 0 : a == 1 ? 3 : a == 2 ? 4 : 4 + D;
+        const int dim = a == 0 ? 3 : a == 1 ? 1 : D;
+        float ur[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ui[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int c = 0; c < dim; ++c) {
+            if ((c & 1) == 0) {
+                if (r_on && e.epoch) uniform4(seed, gid, e.epoch, (uint32_t)(c >> 1), MI_DR_STREAM_PHYS_RESET(a), ur);
+                if (i_on && e.draws) uniform4(seed, gid, e.draws, (uint32_t)(c >> 1), MI_DR_STREAM_PHYS_INTERVAL(a), ui);
+            }
+            const int k = base + c;
+            rec[k] = mi_dr_phys_value(nominal[k], c, r_on, d->r_op[a], d->r_dist[a], prm[k], prm[recw + k],
+                                      e.epoch, ur, i_on, d->i_op[a], d->i_dist[a], prm[2 * recw + k],
+                                      prm[3 * recw + k], e.draws, ui);
+        }
     }
 }
 
@@ -1691,6 +1834,22 @@ int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, 
     hipLaunchKernelGGL(k_init_state, grid_for(s, N), dim3(s->block), 0, 0, st, m.D);
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return cleanup(fail(MI_E_HIP, "init: %s", hipGetErrorString(e)));
+    {   // the sim-wide values in the order of a per-env parameter record (mi_get_env_params
+        // before a table exists, the fill of a new table, the schedules' nominal operand)
+        const int Dm = m.D;
+        s->nominal.assign((size_t)4 + 2 * Dm, 0.0f);
+        for (int k = 0; k < 3; ++k) s->nominal[k] = s->sp.g[k];
+        s->nominal[kEnvpFriction] = s->sp.friction;
+        if (m.dyn == MI_DYN_CARTPOLE) {
+            if (Dm >= 2) { s->nominal[kEnvpDamping] = md->cart_damping; s->nominal[kEnvpDamping + 1] = md->pole_damping; }
+        } else {
+            for (int j = 0; j < Dm; ++j) {
+                s->nominal[kEnvpDamping + j] = md->damping[j + 1];
+                s->nominal[kEnvpDamping + Dm + j] = md->armature[j + 1];
+            }
+        }
+        if ((rc = upload(s, s->nominal.data(), s->nominal.size(), &s->nominal_dev))) return cleanup(rc);
+    }
     if ((rc = sync_kparams(s))) return cleanup(rc);
     if (s->wave && s->lds_bytes > 64 * 1024) {   // above the default dynamic-LDS limit
         hipError_t e1 = hipSuccess, e2 = hipSuccess;
@@ -1800,14 +1959,21 @@ static int launch_sim(mi_sim* s, int substeps, hipStream_t stream) {
                     Mirrors mir{};
                     if (mirrored)
                         for (int k = 0; k < 6; ++k) mir.p[k] = s->mir[k];
-                    hipLaunchKernelGGL(k_sim_step_pair<decltype(T)>, wave_grid(s), wave_block(s), s->lds_bytes,
-                                       stream, (const KParams*)s->kp_dev, substeps, mir);
+                    if (s->envp)
+                        hipLaunchKernelGGL(k_sim_step_pair<EnvP<decltype(T)>>, wave_grid(s), wave_block(s),
+                                           s->lds_bytes, stream, (const KParams*)s->kp_dev, substeps, mir);
+                    else
+                        hipLaunchKernelGGL(k_sim_step_pair<decltype(T)>, wave_grid(s), wave_block(s), s->lds_bytes,
+                                           stream, (const KParams*)s->kp_dev, substeps, mir);
                     return;
                 }
             }
             hipLaunchKernelGGL(k_sim_step_wave<decltype(T)>, wave_grid(s), wave_block(s), s->lds_bytes,
                                stream, (const KParams*)s->kp_dev, substeps);
         });
+    else if (s->envp)
+        hipLaunchKernelGGL(k_sim_step_envp, grid_for(s, s->N), dim3(s->block), 0, stream, s->dm, s->ds,
+                           s->sp, substeps, (const float*)s->envp, s->envp_stride);
     else
         hipLaunchKernelGGL(k_sim_step, grid_for(s, s->N), dim3(s->block), 0, stream, s->dm, s->ds,
                            s->sp, substeps);
@@ -2252,11 +2418,30 @@ int mi_env_step(mi_sim* s, const float* actions, int32_t substeps, float* obs_ou
     HIP_TRY(hipSetDevice(s->device));
     FLUSH(s, stream);
     s->mir_valid = false;
+    // physics DR: step_randomization(reset_inds) with the incoming reset_buf, ahead of the fused
+    // launch on the same stream (in_hand_manipulation.py:271-275: before reset_idx consumes it)
+    if (s->pdr_on)
+        if (int rc = dr_phys_step(s, reset_buf, STREAM(stream))) return rc;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     HIP_TRY(timed_launch(s, stream, &ev0, &ev1));
     if (s->wave && s->tp.kind != MI_TASK_CARTPOLE)
         with_topo(s->topo, s->sp.tgs != 0, [&](auto T) {
             if constexpr (has_pair<decltype(T)>()) {
+                if (s->pair && s->envp) {
+                    using TE = EnvP<decltype(T)>;
+                    if (ev0)
+                        hipExtLaunchKernelGGL(k_env_step_pair<TE>, wave_grid(s), wave_block(s),
+                                              (uint32_t)s->lds_bytes, STREAM(stream), ev0, ev1, 0,
+                                              (const KParams*)s->kp_dev, actions, substeps, obs_out, obs_task,
+                                              rew, reset_buf, progress_buf, potentials, prev_potentials,
+                                              actions_out, rew_out, reset_out);
+                    else
+                        hipLaunchKernelGGL(k_env_step_pair<TE>, wave_grid(s), wave_block(s), s->lds_bytes,
+                                           STREAM(stream), (const KParams*)s->kp_dev, actions, substeps,
+                                           obs_out, obs_task, rew, reset_buf, progress_buf, potentials,
+                                           prev_potentials, actions_out, rew_out, reset_out);
+                    return;
+                }
                 if (s->pair) {
                     if (ev0)
                         hipExtLaunchKernelGGL(k_env_step_pair<decltype(T)>, wave_grid(s), wave_block(s),
@@ -2284,6 +2469,16 @@ int mi_env_step(mi_sim* s, const float* actions, int32_t substeps, float* obs_ou
                                    obs_out, obs_task, rew, reset_buf, progress_buf, potentials,
                                    prev_potentials, actions_out, rew_out, reset_out);
         });
+    else if (s->envp && ev0)
+        hipExtLaunchKernelGGL(k_env_step_envp, grid_for(s, s->N), dim3(s->block), 0u, STREAM(stream), ev0, ev1, 0,
+                              s->dm, s->ds, s->sp, s->tp, actions, substeps, obs_out, obs_task, rew,
+                              reset_buf, progress_buf, potentials, prev_potentials, actions_out, rew_out,
+                              reset_out, (const float*)s->envp, s->envp_stride);
+    else if (s->envp)
+        hipLaunchKernelGGL(k_env_step_envp, grid_for(s, s->N), dim3(s->block), 0, STREAM(stream), s->dm,
+                           s->ds, s->sp, s->tp, actions, substeps, obs_out, obs_task, rew, reset_buf,
+                           progress_buf, potentials, prev_potentials, actions_out, rew_out, reset_out,
+                           (const float*)s->envp, s->envp_stride);
     else if (ev0)
         hipExtLaunchKernelGGL(k_env_step, grid_for(s, s->N), dim3(s->block), 0u, STREAM(stream), ev0, ev1, 0,
                               s->dm, s->ds, s->sp, s->tp, actions, substeps, obs_out, obs_task, rew,
@@ -2385,6 +2580,194 @@ int mi_get_dr_state(mi_sim* s, uint32_t* out) {
     HIP_TRY(hipMemcpy(f.data(), s->ds.dr_state, f.size() * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < s->N; ++i)
         for (int k = 0; k < 6; ++k) out[(size_t)6 * i + k] = f[(size_t)k * s->N + i];
+    return MI_OK;
+}
+
+// ---- per-env physics parameters + physics DR ---------------------------------------------
+static void free_tracked(mi_sim* s, void* p) {
+    if (!p) return;
+    (void)hipFree(p);
+    s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), p), s->allocs.end());
+}
+
+static int envp_check_attr(mi_sim* s, int32_t attr, const char* fn) {
+    if (attr < MI_ENVP_GRAVITY || attr > MI_ENVP_ARMATURE) return fail(MI_E_ARG, "%s: bad attribute %d", fn, attr);
+    if (s->dm.dyn == MI_DYN_CARTPOLE && (attr == MI_ENVP_FRICTION || attr == MI_ENVP_ARMATURE))
+        return fail(MI_E_ARG, "%s: the analytic cart-pole has no %s (it takes gravity and damping = (cart, pole))",
+                    fn, attr == MI_ENVP_FRICTION ? "friction" : "armature");
+    return MI_OK;
+}
+
+// allocate the table on first use, every record = the nominal values
+static int envp_ensure(mi_sim* s, hipStream_t stream, const char* fn) {
+    if (s->envp) return MI_OK;
+    if (s->wave && !s->pair)
+        return fail(MI_E_STATE, "%s: the wavefront-per-env path (MI_WAVE_PAIR=0, runtime tables or an odd env "
+                                "count) has no per-env parameter kernels; use the two-envs-per-wavefront or the "
+                                "one-lane-per-env path", fn);
+    if (capturing(stream)) return fail(MI_E_STATE, "%s: the first call allocates the table: make it before the capture", fn);
+    const int recw = 4 + 2 * s->dm.D;
+    const int stride = (recw + 31) & ~31;
+    void* p = nullptr;
+    if (int rc = dev_alloc(s, &p, sizeof(float) * (size_t)stride * s->N)) return rc;
+    hipLaunchKernelGGL(k_envp_fill, dim3((unsigned)(((int64_t)s->N * stride + 255) / 256)), dim3(256), 0, stream,
+                       (float*)p, stride, recw, s->nominal_dev, s->N);
+    LAUNCH_CHECK();
+    HIP_TRY(hipStreamSynchronize(stream));   // first use only: later calls on any stream see the fill
+    if (s->wave && s->lds_bytes > 64 * 1024) {   // the EnvP instantiations' dynamic-LDS limit
+        hipError_t e1 = hipSuccess, e2 = hipSuccess;
+        with_topo(s->topo, s->sp.tgs != 0, [&](auto T) {
+            if constexpr (has_pair<decltype(T)>()) {
+                e1 = hipFuncSetAttribute((const void*)k_env_step_pair<EnvP<decltype(T)>>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes);
+                e2 = hipFuncSetAttribute((const void*)k_sim_step_pair<EnvP<decltype(T)>>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes);
+            }
+        });
+        if (e1 != hipSuccess || e2 != hipSuccess) {
+            free_tracked(s, p);
+            return fail(MI_E_HIP, "%s: %zu B of LDS per workgroup refused", fn, s->lds_bytes);
+        }
+    }
+    s->envp = (float*)p;
+    s->envp_stride = stride;
+    return sync_kparams(s);
+}
+
+int mi_set_env_params(mi_sim* s, int32_t attr, const float* values, const int64_t* idx, int32_t n, void* stream) {
+    NEED(s); NEED(values);
+    if (int rc = envp_check_attr(s, attr, __func__)) return rc;
+    if (n < 0 || (!idx && n > s->N)) return fail(MI_E_SHAPE, "%s: n %d out of range", __func__, n);
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);      // deferred substeps ran with the parameters of their request
+    if (int rc = envp_ensure(s, STREAM(stream), __func__)) return rc;
+    if (n == 0) return MI_OK;
+    const int D = s->dm.D, dim = envp_dim(attr, D);
+    hipLaunchKernelGGL(k_envp_set, dim3((unsigned)(((int64_t)n * dim + 255) / 256)), dim3(256), 0, STREAM(stream),
+                       s->envp, s->envp_stride, envp_base(attr, D), dim, values, idx, n, s->N);
+    LAUNCH_CHECK();
+    return MI_OK;
+}
+
+int mi_get_env_params(mi_sim* s, int32_t attr, float* out, void* stream) {
+    NEED(s); NEED(out);
+    if (int rc = envp_check_attr(s, attr, __func__)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const int D = s->dm.D, dim = envp_dim(attr, D);
+    hipLaunchKernelGGL(k_envp_get, dim3((unsigned)(((int64_t)s->N * dim + 255) / 256)), dim3(256), 0, STREAM(stream),
+                       (const float*)s->envp, s->envp_stride, envp_base(attr, D), dim, s->nominal_dev, out, s->N);
+    LAUNCH_CHECK();
+    return MI_OK;
+}
+
+int mi_sim_clear_env_params(mi_sim* s) {
+    NEED(s);
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, s->pending_stream);
+    HIP_TRY(hipDeviceSynchronize());
+    s->pdr_on = false;
+    if (s->pdr_state) HIP_TRY(hipMemset(s->pdr_state, 0, sizeof(uint32_t) * 4 * (size_t)s->N));
+    if (!s->envp) return MI_OK;
+    free_tracked(s, s->envp);
+    s->envp = nullptr;
+    s->envp_stride = 0;
+    return sync_kparams(s);
+}
+
+int mi_sim_set_phys_dr(mi_sim* s, const mi_dr_phys_params* dr) {
+    NEED(s);
+    HIP_TRY(hipSetDevice(s->device));
+    const int D = s->dm.D, recw = 4 + 2 * D;
+    PhysDR h{};
+    std::vector<float> prm((size_t)4 * recw, 0.0f);
+    bool any = false;
+    if (dr) {
+        h.min_frequency = dr->min_frequency;
+        for (int a = 0; a < MI_DR_PHYS_ATTRS; ++a)
+            for (int w = 0; w < 2; ++w) {
+                const mi_dr_phys_sched& c = w ? dr->on_interval[a] : dr->on_reset[a];
+                if (!c.enabled) continue;
+                if (int rc = envp_check_attr(s, a, __func__)) return rc;
+                if (c.operation < MI_DR_OP_ADDITIVE || c.operation > MI_DR_OP_DIRECT)
+                    return fail(MI_E_ARG, "physics DR: bad operation %d", c.operation);
+                if (c.distribution < MI_DR_DIST_GAUSSIAN || c.distribution > MI_DR_DIST_LOGUNIFORM)
+                    return fail(MI_E_ARG, "physics DR: bad distribution %d", c.distribution);
+                if (!c.p0 || !c.p1) return fail(MI_E_NULL, "physics DR: null distribution parameters");
+                const int base = envp_base(a, D), dim = envp_dim(a, D);
+                for (int k = 0; k < dim; ++k) {
+                    if (c.distribution == MI_DR_DIST_LOGUNIFORM && !(c.p0[k] > 0.0f && c.p1[k] > 0.0f))
+                        return fail(MI_E_ARG, "physics DR: loguniform needs positive bounds");
+                    prm[(size_t)(2 * w) * recw + base + k] = c.p0[k];
+                    prm[(size_t)(2 * w + 1) * recw + base + k] = c.p1[k];
+                }
+                if (w) {
+                    if (c.frequency_interval < 1)
+                        return fail(MI_E_ARG, "physics DR: on_interval frequency_interval %d < 1", c.frequency_interval);
+                    if (h.any_interval && h.freq != c.frequency_interval)
+                        return fail(MI_E_ARG, "physics DR: on_interval schedules of one sim share one "
+                                              "frequency_interval (%d and %d given)", h.freq, c.frequency_interval);
+                    h.any_interval = 1;
+                    h.freq = c.frequency_interval;
+                    h.i_on[a] = 1; h.i_op[a] = c.operation; h.i_dist[a] = c.distribution;
+                } else {
+                    h.r_on[a] = 1; h.r_op[a] = c.operation; h.r_dist[a] = c.distribution;
+                }
+                any = true;
+            }
+        if (any && dr->min_frequency < 0) return fail(MI_E_ARG, "physics DR: min_frequency %d < 0", dr->min_frequency);
+    }
+    if (!any) {
+        s->pdr_on = false;
+        return MI_OK;
+    }
+    FLUSH(s, s->pending_stream);
+    if (int rc = envp_ensure(s, s->pending_stream, __func__)) return rc;
+    if (!s->pdr_state) {   // first schedule of this sim: zeroed per-env state (dev_alloc clears)
+        void* p = nullptr;
+        if (int rc = dev_alloc(s, &p, sizeof(uint32_t) * 4 * (size_t)s->N)) return rc;
+        s->pdr_state = (uint32_t*)p;
+        if (int rc = dev_alloc(s, &p, sizeof(PhysDR))) return rc;
+        s->pdr_desc = p;
+        if (int rc = dev_alloc(s, &p, sizeof(float) * prm.size())) return rc;
+        s->pdr_prm = (float*)p;
+    }
+    // a schedule kernel in flight on any stream (torch's streams do not order with the null stream's
+    // copy) must not see a half-updated descriptor: configuration waits for the device
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(s->pdr_desc, &h, sizeof h, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->pdr_prm, prm.data(), sizeof(float) * prm.size(), hipMemcpyHostToDevice));
+    s->pdr_on = true;
+    return MI_OK;
+}
+
+static int dr_phys_step(mi_sim* s, const int64_t* reset_buf, hipStream_t stream) {
+    hipLaunchKernelGGL(k_dr_phys_step, dim3((unsigned)((s->N + 255) / 256)), dim3(256), 0, stream, s->N,
+                       s->ds.off, s->ds.seed, s->dm.D, (const PhysDR*)s->pdr_desc, (const float*)s->pdr_prm,
+                       s->nominal_dev, s->pdr_state, s->envp, s->envp_stride, reset_buf);
+    LAUNCH_CHECK();
+    return MI_OK;
+}
+
+int mi_dr_phys_step(mi_sim* s, const int64_t* reset_buf, void* stream) {
+    NEED(s); NEED(reset_buf);
+    if (!s->pdr_on) return MI_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    return dr_phys_step(s, reset_buf, STREAM(stream));
+}
+
+int mi_get_phys_dr_state(mi_sim* s, uint32_t* out) {
+    NEED(s); NEED(out);
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->pdr_state) {
+        memset(out, 0, sizeof(uint32_t) * 4 * (size_t)s->N);
+        return MI_OK;
+    }
+    std::vector<uint32_t> f((size_t)4 * s->N);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(f.data(), s->pdr_state, f.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < s->N; ++i)
+        for (int k = 0; k < 4; ++k) out[(size_t)4 * i + k] = f[(size_t)k * s->N + i];
     return MI_OK;
 }
 

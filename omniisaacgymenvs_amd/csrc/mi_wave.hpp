@@ -490,12 +490,18 @@ MI_D void wave_link_local(const MC& mc, const WaveTabs& t, float* sm, int l) {
 
 // P1b helpers. Root frame: orientation from the root quaternion, origin p0 (the spatial
 // origin), fictitious base acceleration -g (- w x v for a free root).
+// kEnvP: gravity from the env's parameter record ep (mi_topo.hpp EnvP) instead of the sim's.
+template <bool kEnvP = false>
 MI_D void link_root(const WaveTabs& t, const float* sm, const SimP& p, int nr, float (&R)[9],
-                    float (&o)[3], float (&V)[6], float (&A)[6]) {
+                    float (&o)[3], float (&V)[6], float (&A)[6], const float* ep = nullptr) {
     m3_from_quat(sm + t.s_rp + 4, R);
     o[0] = o[1] = o[2] = 0.0f;
     A[0] = A[1] = A[2] = 0.0f;
-    A[3] = -p.g[0]; A[4] = -p.g[1]; A[5] = -p.g[2];
+    if constexpr (kEnvP) {
+        A[3] = -ep[0]; A[4] = -ep[1]; A[5] = -ep[2];
+    } else {
+        A[3] = -p.g[0]; A[4] = -p.g[1]; A[5] = -p.g[2];
+    }
     if (nr) {
         const float* u = sm + t.s_us;
         const float v[3] = {u[0], u[1], u[2]};
@@ -543,10 +549,11 @@ MI_D void link_step(const MC& mc, int nr, const WaveTabs& t, const float* sm, in
 // along its own root-to-l chain (no barriers between tree levels: every lane walks its chain;
 // each step is the same arithmetic a level-by-level sweep would do, so results are identical),
 // then the link's spatial inertia about p0 and Newton-Euler force from the register values.
+template <bool kEnvP = false>
 MI_D void wave_link_forward(const MC& mc, int nr, const WaveTabs& t, float* sm, int l,
-                            const SimP& p) {
+                            const SimP& p, const float* ep = nullptr) {
     float R[9], o[3], V[6], A[6], s[6];
-    link_root(t, sm, p, nr, R, o, V, A);
+    link_root<kEnvP>(t, sm, p, nr, R, o, V, A, ep);
     for (int j = mc.chain_start(l); j < mc.chain_start(l + 1); ++j)
         link_step(mc, nr, t, sm, mc.chain(j), R, o, V, A, s);
     if (l > 0) {

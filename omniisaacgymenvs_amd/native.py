@@ -81,6 +81,21 @@ class MiDrParams(C.Structure):
                 ("act_on_reset", MiDrNoise), ("act_on_interval", MiDrNoise)]
 
 
+MI_DR_OP_DIRECT = 2
+MI_ENVP_GRAVITY, MI_ENVP_FRICTION, MI_ENVP_DAMPING, MI_ENVP_ARMATURE = 0, 1, 2, 3
+
+
+class MiDrPhysSched(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("operation", C.c_int32), ("distribution", C.c_int32),
+                ("frequency_interval", C.c_int32), ("p0", _f32p), ("p1", _f32p)]
+
+
+class MiDrPhysParams(C.Structure):
+    """mi_dr_phys_params: on_reset / on_interval indexed by MI_ENVP_*."""
+    _fields_ = [("on_reset", MiDrPhysSched * 4), ("on_interval", MiDrPhysSched * 4),
+                ("min_frequency", C.c_int32)]
+
+
 def fptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(_f32p)
 
@@ -131,6 +146,12 @@ _SIGS = {
     "mi_dr_apply_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_dr_apply_observations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_get_dr_state": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi_set_env_params": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mi_get_env_params": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mi_sim_clear_env_params": (C.c_int, [C.c_void_p]),
+    "mi_sim_set_phys_dr": (C.c_int, [C.c_void_p, C.POINTER(MiDrPhysParams)]),
+    "mi_dr_phys_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_get_phys_dr_state": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mi_fill_uniform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64,
                                   C.c_float, C.c_float, C.c_void_p]),
     "mi_get_reset_count": (C.c_int, [C.c_void_p, C.c_void_p]),

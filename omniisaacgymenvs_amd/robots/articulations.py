@@ -271,6 +271,60 @@ class ArticulationView:
     def set_velocities(self, velocities: torch.Tensor, indices=None) -> None:
         self._set_root_state(None, None, self._f32(velocities), indices)
 
+    # ---- per-env physics parameters (include/mi_sim.h mi_set_env_params) ----
+    # The values omni.replicator.isaac's physics_view randomizes through the PhysX views
+    # (randomize.py:308-430): gravity (SimulationContext), one friction coefficient per env
+    # (material_properties' dynamic friction), joint damping (set_gains kds) and armature
+    # (set_armatures). The first setter allocates the sim's per-env table.
+    def _set_env_param(self, attr: int, values, indices) -> None:
+        v = self._f32(torch.as_tensor(values, device=self.device))
+        idx, n = self._idx(indices, torch.int64)
+        if n == 0:
+            return
+        dim = {N.MI_ENVP_GRAVITY: 3, N.MI_ENVP_FRICTION: 1}.get(attr, self.num_dof)
+        if v.numel() != n * dim:        # the kernel trusts the shape
+            raise ValueError(f"{tuple(v.shape)} values for {n} envs x {dim}")
+        N.check(self._lib.mi_set_env_params(self.handle, attr, v.data_ptr(), None if idx is None else idx.data_ptr(),
+                                            n, self.stream()), "mi_set_env_params")
+
+    def _get_env_param(self, attr: int, dim: int, indices) -> torch.Tensor:
+        out = self._empty(self.count, dim)
+        N.check(self._lib.mi_get_env_params(self.handle, attr, out.data_ptr(), self.stream()), "mi_get_env_params")
+        return out if indices is None else out[torch.as_tensor(indices, device=self.device).long()]
+
+    def set_env_gravity(self, gravity, indices=None) -> None:
+        self._set_env_param(N.MI_ENVP_GRAVITY, gravity, indices)
+
+    def get_env_gravity(self, indices=None) -> torch.Tensor:
+        return self._get_env_param(N.MI_ENVP_GRAVITY, 3, indices)
+
+    def set_friction_coefficients(self, values, indices=None) -> None:
+        self._set_env_param(N.MI_ENVP_FRICTION, values, indices)
+
+    def get_friction_coefficients(self, indices=None) -> torch.Tensor:
+        return self._get_env_param(N.MI_ENVP_FRICTION, 1, indices)
+
+    def set_joint_dampings(self, values, indices=None) -> None:
+        self._set_env_param(N.MI_ENVP_DAMPING, values, indices)
+
+    def get_joint_dampings(self, indices=None) -> torch.Tensor:
+        return self._get_env_param(N.MI_ENVP_DAMPING, self.num_dof, indices)
+
+    def set_armatures(self, values, indices=None) -> None:
+        self._set_env_param(N.MI_ENVP_ARMATURE, values, indices)
+
+    def get_armatures(self, indices=None) -> torch.Tensor:
+        return self._get_env_param(N.MI_ENVP_ARMATURE, self.num_dof, indices)
+
+    def clear_env_params(self) -> None:
+        N.check(self._lib.mi_sim_clear_env_params(self.handle), "mi_sim_clear_env_params")
+
+    def phys_dr_state(self) -> np.ndarray:
+        """[count, 4] uint32 physics DR schedule state: since, counter, epoch, draws."""
+        out = np.zeros((self.count, 4), np.uint32)
+        N.check(self._lib.mi_get_phys_dr_state(self.handle, out.ctypes.data), "mi_get_phys_dr_state")
+        return out
+
     # ---- physics ----
     def sim_step(self, substeps: int = 1) -> None:
         N.check(N.lib().mi_sim_step(self.handle, int(substeps), self.stream()), "mi_sim_step")

@@ -168,6 +168,13 @@ class RLTask:
         if self._dr_randomizer.randomize:
             self._dr_randomizer.set_up_domain_randomization(self)
 
+    def _step_physics_dr(self) -> None:
+        """Physics DR's step_randomization(reset_inds) on the method-by-method path, before
+        reset_idx consumes reset_buf (in_hand_manipulation.py:271-275); the fused step issues it
+        inside mi_env_step."""
+        if self._dr_randomizer.randomize:
+            self._dr_randomizer.step_physics_randomization(self.reset_buf)
+
     def _step_outputs(self, out=None):
         """(obs, rew, reset) buffers a fused launch writes its returned copies into: fresh
         tensors (_process_data's clones), or caller-provided views such as a rollout slab row

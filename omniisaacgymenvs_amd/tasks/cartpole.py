@@ -98,6 +98,7 @@ class CartpoleTask(RLTask):
             indices = torch.arange(self._cartpoles.count, dtype=torch.int32)
             self._cartpoles.set_joint_efforts(forces, indices=indices)
             return
+        self._step_physics_dr()
         a = actions.to(self._device, dtype=torch.float32).contiguous()
         N.check(N.lib().mi_task_pre_step(self._h(), a.data_ptr(), self.reset_buf.data_ptr(),
                                          self.progress_buf.data_ptr(), None, None, None,

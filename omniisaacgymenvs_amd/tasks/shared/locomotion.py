@@ -110,6 +110,7 @@ class LocomotionTask(RLTask):
         return {self._robots.name: {"obs_buf": self.obs_buf}}
 
     def pre_physics_step(self, actions) -> None:
+        self._step_physics_dr()
         a = actions.to(self._device, dtype=torch.float32).contiguous()
         N.check(N.lib().mi_task_pre_step(self._h(), a.data_ptr(), self.reset_buf.data_ptr(),
                                          self.progress_buf.data_ptr(), self.potentials.data_ptr(),
