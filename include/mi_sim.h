@@ -394,6 +394,10 @@ int mi_sim_nan_count(mi_sim* sim, int64_t* count);
  * topology: id of the compile-time (model-specialised) topology, 0 = runtime tables;
  * lds_bytes: LDS per env (= per workgroup) of the wave path. Any output may be NULL. */
 int mi_sim_kernel_path(const mi_sim* sim, int32_t* path, int32_t* topology, int32_t* lds_bytes);
+/* Diagnostics: rows of an env's W matrix (one per constraint row of a substep) that the wave
+ * paths keep in LDS; a substep with more rows puts the rest in the env's global slab. 0 on the
+ * one-lane-per-env path. */
+int mi_sim_w_rows_lds(const mi_sim* sim, int32_t* rows);
 int mi_abi_version(void);
 /* SHA-256 (hex) of the sources this library was compiled from: csrc/mi_sim.hip, the csrc .hpp headers and
  * the include headers in name order (__graft_entry__.source_hash); "unknown" when built without it. A

@@ -267,7 +267,16 @@ MI_D int pw_idx(int r, int c, int nv) { return (r & ~3) * nv + 4 * c + (r & 3); 
 // WNV (32) columns: entry (r, c) at (r & ~3) WNV + 4 c + (r & 3), so a slab group is one
 // global_load_dwordx4 per DOF as well (column WNV - 1 is the fallback sweeps' lambda slot)
 MI_D size_t pair_sidx(int r, int c) { return (size_t)(r & ~3) * WNV + 4 * c + (r & 3); }
-typedef const pv4* glb_cf4;
+// Global-typed pointers: the slab pointer (like every pointer the kernels fetch from the
+// parameter block in memory) reaches the code as a generic pointer, and an access through a
+// generic pointer is a flat op, which counts in vmcnt AND lgkmcnt: every LDS wait behind one also
+// waited for its L2 / HBM round trip. Through these types the accesses are global_load /
+// global_store (vmcnt only). Typed where the pointer is formed (glb_ptr, make_wsrc).
+typedef const float __attribute__((address_space(1)))* glb_cf;
+typedef float __attribute__((address_space(1)))* glb_f;
+typedef const pv4 __attribute__((address_space(1)))* glb_cf4;
+MI_D glb_cf glb_ptr(const float* p) { return (glb_cf)p; }
+MI_D glb_f glb_ptr(float* p) { return (glb_f)p; }
 
 // The W-row sources of one env for a PGS phase, read from the parameter block ONCE: through
 // WaveTabs every 4-row group re-read w_rows_lds / s_W with a scalar load and waited for it
@@ -275,10 +284,10 @@ typedef const pv4* glb_cf4;
 // kLds: the narrow path, whose rows are all LDS rows (host-checked: w_rows_lds >= kLamRows).
 struct WSrc {
     lds_cf W;          // the env's LDS W rows
-    const float* gW;   // the env's slab (rows >= nl)
+    glb_cf gW;         // the env's slab (rows >= nl)
     int nl;            // LDS rows
 };
-MI_D WSrc make_wsrc(const WaveTabs& t, const float* sm, const float* gW) {
+MI_D WSrc make_wsrc(const WaveTabs& t, const float* sm, glb_cf gW) {
     WSrc w;
     w.W = lds_ptr(sm + t.s_W);
     int nl = t.w_rows_lds;
@@ -354,9 +363,10 @@ MI_D void pair_wcol_w(const WSrc& ws, int g0, int kc, int nv, float (&wq)[4]) {
 // One articulated substep of the env of this lane's half (env i, LDS region sm, W slab gW).
 template <class TP>
 MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevState& st,
-                             const SimP& p, int i, int wv_, const float* mcb, float* sm, float* gW,
+                             const SimP& p, int i, int wv_, const float* mcb, float* sm, float* gW_,
                              bool load_state, bool store_state, int& prio, int& load,
                              const float* ep = nullptr) {
+    const glb_f gW = glb_ptr(gW_);   // every slab access below is a global op, not a flat one
     // ep (TP::kEnvP only): env i's record of the per-env parameter table. LDS and registers are
     // both full here (Humanoid: 432 B of LDS spare per workgroup, 2 waves / SIMD), so the record
     // is not kept across the substep: its lines are read where the state's effort line is (P3:
@@ -972,7 +982,7 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
             }
             // the env of half h: its slab (the pair need not be adjacent envs: pairing by load)
             const int ih = __builtin_amdgcn_readlane(i, 32 * h);
-            const float* gWh = gW + (ptrdiff_t)(ih - i) * (ptrdiff_t)t.g_row_stride;
+            const glb_cf gWh = gW + (ptrdiff_t)(ih - i) * (ptrdiff_t)t.g_row_stride;
             const WSrc wsh = make_wsrc(t, smh, gWh);
             const int rl = l64 < nrh ? l64 : 0;
             float Jr[TP::nvc];
@@ -1072,7 +1082,10 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
                 constexpr int g0 = 4 * G;
                 float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                 if (g0 < nrh) {
-                    pair_dgroup_w<TP, MI_PAIR_WIDE_PD, false>(wsh, g0, nrh, Jr, a);
+                    // groups wholly below kLamRows are LDS rows in every layout the host accepts
+                    // (mi_sim.hip: "paired wave layout: ... LDS W rows < ... Delassus rows", and
+                    // w_rows_lds a multiple of 4): no slab branch compiled for them
+                    pair_dgroup_w<TP, MI_PAIR_WIDE_PD, (g0 + 3 < TP::kLamRows)>(wsh, g0, nrh, Jr, a);
                     if constexpr (g0 >= AR) {
 #pragma unroll
                         for (int q = 0; q < 4; ++q)
@@ -1187,7 +1200,7 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
             // the next group's W column is loaded before this group's FMAs (rows past the LDS
             // ones come from the slab: one L2 round trip per group on the chain otherwise)
             float wn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            pair_wcol_w<false>(wsh, 0, kc, NV, wn);
+            pair_wcol_w<(3 < TP::kLamRows)>(wsh, 0, kc, NV, wn);
 #endif
             sfor<0, 16>([&](auto G) {
                 constexpr int g0 = 4 * G;
@@ -1197,9 +1210,9 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
 #pragma unroll
                     for (int q = 0; q < 4; ++q) wq[q] = wn[q];
                     if constexpr (g0 + 4 < 64)
-                        if (g0 + 4 < nrh) pair_wcol_w<false>(wsh, g0 + 4, kc, NV, wn);
+                        if (g0 + 4 < nrh) pair_wcol_w<(g0 + 7 < TP::kLamRows)>(wsh, g0 + 4, kc, NV, wn);
 #else
-                    pair_wcol_w<false>(wsh, g0, kc, NV, wq);
+                    pair_wcol_w<(g0 + 3 < TP::kLamRows)>(wsh, g0, kc, NV, wq);
 #endif
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
@@ -1260,8 +1273,10 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
         const int nnorm = 3 * ncon;
         // W entry of row rr at the lane's DOF (uniform branch: LDS rows, then the slab); read
         // per row (a handful of substeps in a million: registers matter more than latency here)
-        const float* wsm = sm;
-        const float* wgW = gW;
+        // (typed pointers: laundered through the asm below as generic ones, both sides of the
+        // select were flat loads)
+        lds_cf wsm = lds_ptr(sm);
+        glb_cf wgW = gW;
         auto wrow = [&](int rr) {
             return (rr < t.w_rows_lds ? wsm[t.s_W + pw_idx(rr, kc, nv)] : wgW[pair_sidx(rr, kc)]) * kin;
         };
@@ -1336,7 +1351,7 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
                 }
                 jc *= kin;
                 const float jv = psum(jc * u);
-                float* lp = gW + pair_sidx(rs, WNV - 1);
+                const glb_f lp = gW + pair_sidx(rs, WNV - 1);
                 const float l0 = live_row ? *lp : 0.0f;
                 float brt = br;
                 if constexpr (TP::kTgs)

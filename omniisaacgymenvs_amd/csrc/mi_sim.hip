@@ -996,6 +996,11 @@ template <class T>
 __global__ __launch_bounds__(512) MI_PAIR_OCC void k_sim_step_pair(const KParams* __restrict__ kp, int substeps,
                                                     Mirrors mir) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    // the block's pointers (state, task, tables, slab) are loaded through the constant address
+    // space, which marks them global: fetched through the kernel's own (global) argument they
+    // are generic pointers and every access through them a flat op, which also counts as an
+    // LDS op in the wave's waits
+    kp = opaque_kp(kp);
     const WaveTabs& t = kp->t;
     const bool live = pair_live(kp->st.N);
     const int i = live ? pair_env_by_load(kp->st) : pair_env();
@@ -1038,6 +1043,11 @@ __global__ __launch_bounds__(512) MI_PAIR_OCC void k_env_step_pair(const KParams
                                                     float* pot, float* prev, float* actions_out,
                                                     float* rew_out, int64_t* reset_out) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    // the block's pointers (state, task, tables, slab) are loaded through the constant address
+    // space, which marks them global: fetched through the kernel's own (global) argument they
+    // are generic pointers and every access through them a flat op, which also counts as an
+    // LDS op in the wave's waits
+    kp = opaque_kp(kp);
     const DevModel& m = kp->m;
     const WaveTabs& t = kp->t;
     const DevState& st = kp->st;
@@ -2833,6 +2843,13 @@ int mi_sim_kernel_path(const mi_sim* s, int32_t* path, int32_t* topology, int32_
     // per env: the workgroup's LDS (shared constants + envs_per_wg env regions) / envs_per_wg
     if (lds_bytes) *lds_bytes = s->wave ? (int32_t)(s->lds_bytes / s->wt.envs_per_wg) : 0;
     if (path && s->pair) *path = 2;
+    return MI_OK;
+}
+
+int mi_sim_w_rows_lds(const mi_sim* s, int32_t* rows) {
+    NEED(s);
+    if (!rows) return fail(MI_E_ARG, "mi_sim_w_rows_lds: rows is NULL");
+    *rows = s->wave ? s->wt.w_rows_lds : 0;
     return MI_OK;
 }
 
