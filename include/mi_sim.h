@@ -198,6 +198,24 @@ int mi_set_dof_state_i32(mi_sim* sim, const float* q /*[n,D]|NULL*/, const float
 int mi_set_root_state_i32(mi_sim* sim, const float* pos /*[n,3]|NULL*/, const float* quat /*[n,4]|NULL*/,
                           const float* vel /*[n,6]|NULL*/, const int32_t* idx /*[n]|NULL*/, int32_t n,
                           void* stream);
+/* --- link-frame view: RigidPrimView over the articulation's bodies (knees and feet,
+ *     tasks/anymal_terrain.py:293-307; hand and finger frames, tasks/franka_cabinet.py:197-217) ---
+ * K frames, each rigidly attached to a link: frame k sits at link_ids[k] with origin offsets[k]
+ * (link frame; NULL = link origins) and the link's orientation. Outputs row-major, any may be NULL:
+ * pos [N,K,3] world, quat [N,K,4] wxyz, vel [N,K,6] = linear velocity of the frame origin, angular
+ * velocity (world axes) — root_state's conventions, so frame (link 0, offset 0) IS mi_get_root_state
+ * (a fixed base has no root velocity: its frames' velocities come from qd alone).
+ * Both calls issue deferred substeps like the other getters, are stream-ordered, do not block the
+ * host and do not allocate (capturable); link_ids and offsets are HOST arrays that travel by value
+ * in the kernel argument block. They only read the state. 1 <= K <= L, else MI_E_SHAPE; an id
+ * outside [0, L) is MI_E_ARG. */
+int mi_get_link_state(mi_sim* sim, const int32_t* link_ids /*host [K]*/, const float* offsets /*host [K,3]|NULL*/,
+                      int32_t K, float* pos, float* quat, float* vel, void* stream);
+/* jac [N,K,6,nv]: rows lin(3), ang(3) of the same frames; columns = the generalized velocity
+ * u = (root lin, root ang (world), qd[D]) for a floating root (nv = D+6), qd[D] for a fixed one.
+ * vel[n,k] == jac[n,k] @ u[n]. Columns of DOFs that do not move the frame are exactly 0. */
+int mi_get_link_jacobian(mi_sim* sim, const int32_t* link_ids, const float* offsets, int32_t K,
+                         float* jac, void* stream);
 /* State mirrors: row-major copies of the articulation state in caller-owned device buffers, the
  * tensors ArticulationView getters hand out with clone=False (get_world_poses, get_velocities,
  * get_joint_positions / velocities, _physics_view.get_force_sensor_forces: locomotion.py:81-89;

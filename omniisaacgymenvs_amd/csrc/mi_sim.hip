@@ -20,6 +20,7 @@
 #include "mi_task.hpp"
 #include "mi_wave.hpp"
 #include "mi_pair.hpp"
+#include "mi_link.hpp"
 
 using namespace mi;
 
@@ -2071,6 +2072,53 @@ int mi_get_sensor_wrench(mi_sim* s, float* out, void* stream) {
     GFields f{};
     f.f[0] = {s->ds.sens, out, 6 * s->dm.S, s->ds.sfs, s->ds.ses};
     return gather_fields(s, f, 1, stream);
+}
+
+// --- link-frame view (mi_link.hpp): reads the state only, so the mirrors stay valid ---
+static int link_request(mi_sim* s, const char* fn, const int32_t* ids, const float* offs, int32_t K, LinkReq* rq) {
+    if (!ids) return fail(MI_E_NULL, "%s: null link_ids", fn);
+    if (K <= 0 || K > s->dm.L) return fail(MI_E_SHAPE, "%s: K=%d frames (expected 1..%d, the model's links)", fn, K, s->dm.L);
+    for (int k = 0; k < K; ++k)
+        if (ids[k] < 0 || ids[k] >= s->dm.L)
+            return fail(MI_E_ARG, "%s: link_ids[%d]=%d is not a link (0..%d)", fn, k, ids[k], s->dm.L - 1);
+    memset(rq, 0, sizeof *rq);
+    rq->K = K;
+    rq->has_off = offs != nullptr;
+    for (int k = 0; k < K; ++k) rq->link[k] = ids[k];
+    if (offs) memcpy(rq->off, offs, sizeof(float) * 3 * (size_t)K);
+    return MI_OK;
+}
+
+int mi_get_link_state(mi_sim* s, const int32_t* link_ids, const float* offsets, int32_t K, float* pos, float* quat,
+                      float* vel, void* stream) {
+    NEED(s);
+    LinkReq rq;
+    int rc = link_request(s, __func__, link_ids, offsets, K, &rq);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    if (!pos && !quat && !vel) return MI_OK;
+    const dim3 grid((s->N + kLinkStateEnvs - 1) / kLinkStateEnvs);
+    hipLaunchKernelGGL(k_link_state, grid, dim3(kLinkThreads), link_state_lds(s->dm.D, K), STREAM(stream), s->dm,
+                       s->ds, rq, pos, quat, vel);
+    LAUNCH_CHECK();
+    return MI_OK;
+}
+
+int mi_get_link_jacobian(mi_sim* s, const int32_t* link_ids, const float* offsets, int32_t K, float* jac,
+                         void* stream) {
+    NEED(s); NEED(jac);
+    LinkReq rq;
+    int rc = link_request(s, __func__, link_ids, offsets, K, &rq);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    if (s->dm.nv == 0) return MI_OK;               // a model without DOFs has empty Jacobians
+    const dim3 grid((s->N + kLinkJacEnvs - 1) / kLinkJacEnvs);
+    hipLaunchKernelGGL(k_link_jacobian, grid, dim3(kLinkThreads), link_jac_lds(s->dm.D, s->dm.nv, K),
+                       STREAM(stream), s->dm, s->ds, rq, jac);
+    LAUNCH_CHECK();
+    return MI_OK;
 }
 
 int mi_set_dof_efforts(mi_sim* s, const float* eff, const int32_t* idx, int32_t n, void* stream) {

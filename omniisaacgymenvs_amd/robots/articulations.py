@@ -15,6 +15,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import re
 from typing import Optional
 
 import numpy as np
@@ -197,6 +198,58 @@ class ArticulationView:
         self._refresh_mirror()
         return self._out(self._mir_qd, indices, clone)
 
+    # ---- bodies: link-frame view (include/mi_sim.h mi_get_link_state / mi_get_link_jacobian) ----
+    @property
+    def body_names(self):
+        return list(self.model.body_names)
+
+    @property
+    def num_bodies(self) -> int:
+        return self.model.num_bodies
+
+    def get_body_index(self, name: str) -> int:
+        return self.model.get_body_index(name)
+
+    @property
+    def num_gen_vel(self) -> int:
+        """nv: columns of a Jacobian — (root lin, root ang, qd) for a floating root, else qd."""
+        return self.num_dof + (6 if self.model.root_free else 0)
+
+    def _frames(self, body_names):
+        """(link ids int32 [K], offsets float32 [K,3]) of the named bodies' frames (None: all)."""
+        m = self.model
+        ids = range(m.num_bodies) if body_names is None else [m.get_body_index(b) for b in body_names]
+        ids = list(ids)
+        return (np.ascontiguousarray(m.body_link[ids], dtype=np.int32),
+                np.ascontiguousarray(m.body_offset[ids], dtype=np.float32))
+
+    def get_link_view(self, body_names, name: str = "link_view") -> "RigidPrimView":
+        """RigidPrimView over the named bodies of every env (prims env-major: env 0's bodies in the
+        given order, then env 1's, ...)."""
+        if isinstance(body_names, RigidPrimView):
+            # built from a prim path expression: its last component names the bodies, as a
+            # regular expression the way the reference's views use it (".../anymal/.*_SHANK")
+            view = body_names
+            pat = re.compile(view.prim_paths_expr.rstrip("/").split("/")[-1])
+            body_names = [b for b in self.model.body_names if pat.fullmatch(b)]
+            if not body_names:
+                raise KeyError(f"{view.prim_paths_expr!r} matches no body; bodies: {', '.join(self.model.body_names)}")
+        else:
+            if isinstance(body_names, str):
+                body_names = [body_names]
+            view = RigidPrimView(name=name)
+        view._bind(self, list(body_names))
+        return view
+
+    def get_jacobians(self, body_names=None) -> torch.Tensor:
+        """[count, K, 6, nv] Jacobians of the named bodies' frames (all bodies by default): rows
+        linear (3), angular (3), world axes; columns the generalized velocity."""
+        links, offs = self._frames(body_names)
+        out = self._empty(self.count, links.shape[0], 6, self.num_gen_vel)
+        N.check(self._lib.mi_get_link_jacobian(self.handle, N.iptr(links), N.fptr(offs), links.shape[0],
+                                               out.data_ptr(), self.stream()), "mi_get_link_jacobian")
+        return out
+
     # ---- setters (indices: env ids, rows of the value tensors align with them) ----
     @staticmethod
     def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -354,3 +407,57 @@ class ArticulationView:
         c = C.c_int64()
         N.check(N.lib().mi_sim_nan_count(self.handle, C.byref(c)), "mi_sim_nan_count")
         return int(c.value)
+
+
+class RigidPrimView:
+    """omni.isaac.core's RigidPrimView over bodies of an articulation (knees and feet,
+    tasks/anymal_terrain.py:293-307; hand and finger frames, tasks/franka_cabinet.py:197-217):
+    K bodies in each of N envs are ``count = N K`` prims, env-major, so callers can
+    ``.view(N, K, ...)``. Every getter is one mi_get_link_state launch on torch's current stream.
+    The view owns its output tensors and hands them out like the state mirrors: with clone=False
+    the buffer itself, which the next read overwrites. Read-only: bodies are moved through their
+    articulation. Built by ``ArticulationView.get_link_view(body_names)``, or the reference's way,
+    ``RigidPrimView(prim_paths_expr=".../<Robot>/<body>", name=...)``, then bound with
+    ``ArticulationView.get_link_view(view)``."""
+
+    def __init__(self, prim_paths_expr: str = "", name: str = "rigid_prim_view", reset_xform_properties: bool = False):
+        self.prim_paths_expr = prim_paths_expr
+        self.name = name
+        self.count = 0
+        self._art = None
+
+    def _bind(self, art: ArticulationView, body_names) -> None:
+        if art.handle is None:
+            raise RuntimeError("the articulation view is not initialized")
+        self._art = art
+        self.body_names = list(body_names)
+        self._links, self._offs = art._frames(self.body_names)
+        self.num_bodies = K = len(self.body_names)
+        self.count = art.count * K
+        self.device = art.device
+        self._pos, self._rot, self._vel = art._empty(self.count, 3), art._empty(self.count, 4), art._empty(self.count, 6)
+
+    def _read(self, pos, rot, vel) -> None:
+        a = self._art
+        if a is None:
+            raise RuntimeError(f"RigidPrimView {self.name!r} is not bound: ArticulationView.get_link_view(view)")
+        rc = a._lib.mi_get_link_state(a.handle, N.iptr(self._links), N.fptr(self._offs), self.num_bodies,
+                                      N.ptr(pos), N.ptr(rot), N.ptr(vel), a.stream())
+        if rc:
+            N.check(rc, "mi_get_link_state")
+
+    def get_world_poses(self, indices=None, clone: bool = True):
+        """([count, 3] positions, [count, 4] wxyz orientations) of the prims (``indices``: prims)."""
+        self._read(self._pos, self._rot, None)
+        return ArticulationView._out(self._pos, indices, clone), ArticulationView._out(self._rot, indices, clone)
+
+    def get_velocities(self, indices=None, clone: bool = True) -> torch.Tensor:
+        """[count, 6]: linear velocity of the body origin, angular velocity (world axes)."""
+        self._read(None, None, self._vel)
+        return ArticulationView._out(self._vel, indices, clone)
+
+    def get_linear_velocities(self, indices=None, clone: bool = True) -> torch.Tensor:
+        return self.get_velocities(indices, clone=False)[:, :3].clone()
+
+    def get_angular_velocities(self, indices=None, clone: bool = True) -> torch.Tensor:
+        return self.get_velocities(indices, clone=False)[:, 3:].clone()

@@ -156,6 +156,11 @@ class CompiledModel:
     body_of_link: List[str]
     dyn_kind: int = N.MI_DYN_ARTICULATION
     cartpole: Dict[str, float] = dataclasses.field(default_factory=dict)
+    # the bodies that remain after welding, BFS order: body b's frame rides on link body_link[b]
+    # (the last link of its chain) with its origin at body_offset[b] in that link's frame
+    body_names: List[str] = dataclasses.field(default_factory=list)
+    body_link: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.int32))
+    body_offset: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros((0, 3)))
 
     @property
     def num_links(self) -> int:
@@ -179,6 +184,16 @@ class CompiledModel:
 
     def get_dof_index(self, name: str) -> int:
         return self.dof_names.index(name)
+
+    @property
+    def num_bodies(self) -> int:
+        return len(self.body_names)
+
+    def get_body_index(self, name: str) -> int:
+        try:
+            return self.body_names.index(name)
+        except ValueError:
+            raise KeyError(f"no body {name!r} after welding; bodies: {', '.join(self.body_names)}") from None
 
     def total_mass(self) -> float:
         return float(self.mass.sum())
@@ -527,6 +542,9 @@ def compile_mjcf(path: str, sensor_bodies: Optional[List[str]] = None,
         geom_p0=f(g0, (-1, 3)), geom_p1=f(g1, (-1, 3)), geom_radius=f(gr, (-1,)),
         sensor_link=np.array(sl, dtype=np.int32), sensor_pos=f(sp, (-1, 3)), pairs=pairs,
         dof_names=dof_names, link_names=link_names, body_of_link=body_of_link,
+        body_names=[b.name for b in order],
+        body_link=np.array([last_link[b.name] for b in order], dtype=np.int32),
+        body_offset=f([0.0 - last_anchor[b.name] for b in order], (-1, 3)),
     )
 
 
