@@ -216,6 +216,33 @@ int mi_get_link_state(mi_sim* sim, const int32_t* link_ids /*host [K]*/, const f
  * vel[n,k] == jac[n,k] @ u[n]. Columns of DOFs that do not move the frame are exactly 0. */
 int mi_get_link_jacobian(mi_sim* sim, const int32_t* link_ids, const float* offsets, int32_t K,
                          float* jac, void* stream);
+/* --- dynamics view: ArticulationView.get_mass_matrices / get_coriolis_and_centrifugal_forces /
+ *     get_generalized_gravity_forces, the terms a task-layer controller needs next to
+ *     mi_get_link_jacobian (gravity compensation, computed torque, operational space) ---
+ * Any output may be NULL, not all three (MI_E_NULL). Row-major:
+ *   M    [N,nv,nv]  joint-space inertia of the rigid-body tree
+ *   cor  [N,nv]     velocity-product (Coriolis / centrifugal) forces c(q,u)
+ *   grav [N,nv]     generalized gravity forces g(q)
+ * with  M u' + c + g = tau  for u = (root lin, root ang (world), qd[D]) (floating root,
+ * nv = D+6) or qd[D] (fixed root): the generalized velocity of mi_get_link_jacobian.
+ * M is the pure rigid-body inertia, sum_l J_l^T diag(m_l, I_l^world) J_l with J_l =
+ * mi_get_link_jacobian of link l at offset com[l]: no armature and no dt * damping (the stepper
+ * adds both to its own M; read them with mi_get_env_params / the model). Massless links contribute
+ * nothing. M[j][k] is exactly 0 when neither DOF is an ancestor of the other, and M[j][k],
+ * M[k][j] are the same bits.
+ * c is the generalized force that holds u' = 0 at gravity 0: sum_l J_l^T (m_l a_l, I_l w'_l +
+ * w_l x I_l w_l) with a_l / w'_l the centre-of-mass and angular accelerations the links have
+ * while u is held constant. The per-link angular damping (mi_sim_params.angular_damping) and the
+ * joint damping are NOT part of c.
+ * g = -sum_l m_l J_lin,l^T gravity: for gravity (0,0,-9.81) the root's z entry is +9.81 * total
+ * mass. With a per-env parameter table (mi_set_env_params, MI_ENVP_GRAVITY) g uses the gravity of
+ * each env's record, else mi_sim_params.gravity; M and c never depend on the table.
+ * Like the other getters the call issues deferred substeps, is stream-ordered, does not block the
+ * host and does not allocate (capturable; a captured call keeps reading the parameter table it
+ * was captured with). It only reads the state. Every model mi_sim_create accepts, both state
+ * layouts; the analytic cart-pole is computed from its link tree like any other fixed-base model.
+ * No atomics: the outputs are the same bits on every run. */
+int mi_get_dynamics(mi_sim* sim, float* M, float* cor, float* grav, void* stream);
 /* State mirrors: row-major copies of the articulation state in caller-owned device buffers, the
  * tensors ArticulationView getters hand out with clone=False (get_world_poses, get_velocities,
  * get_joint_positions / velocities, _physics_view.get_force_sensor_forces: locomotion.py:81-89;

@@ -21,6 +21,7 @@
 #include "mi_wave.hpp"
 #include "mi_pair.hpp"
 #include "mi_link.hpp"
+#include "mi_dyn.hpp"
 
 using namespace mi;
 
@@ -2117,6 +2118,25 @@ int mi_get_link_jacobian(mi_sim* s, const int32_t* link_ids, const float* offset
     const dim3 grid((s->N + kLinkJacEnvs - 1) / kLinkJacEnvs);
     hipLaunchKernelGGL(k_link_jacobian, grid, dim3(kLinkThreads), link_jac_lds(s->dm.D, s->dm.nv, K),
                        STREAM(stream), s->dm, s->ds, rq, jac);
+    LAUNCH_CHECK();
+    return MI_OK;
+}
+
+// --- dynamics view (mi_dyn.hpp): M, c, g of the rigid-body tree; reads the state (and the per-env
+// gravity, when the parameter table exists) only ---
+int mi_get_dynamics(mi_sim* s, float* M, float* cor, float* grav, void* stream) {
+    NEED(s);
+    if (!M && !cor && !grav) return fail(MI_E_NULL, "mi_get_dynamics: M, cor and grav are all null");
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    if (s->dm.nv == 0) return MI_OK;               // a model without DOFs has empty outputs
+    DynGravity gv;
+    for (int c = 0; c < 3; ++c) gv.g[c] = s->sp.g[c];
+    gv.envp = s->envp;
+    gv.stride = s->envp_stride;
+    const dim3 grid((s->N + kDynEnvs - 1) / kDynEnvs);
+    hipLaunchKernelGGL(k_dynamics, grid, dim3(kLinkThreads), dyn_lds(s->dm.D, s->dm.L, s->dm.nv), STREAM(stream),
+                       s->dm, s->ds, gv, M, cor, grav);
     LAUNCH_CHECK();
     return MI_OK;
 }

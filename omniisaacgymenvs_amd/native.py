@@ -121,6 +121,7 @@ _SIGS = {
     "mi_get_link_state": (C.c_int, [C.c_void_p, _i32p, _f32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "mi_get_link_jacobian": (C.c_int, [C.c_void_p, _i32p, _f32p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mi_get_dynamics": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4),
     "mi_set_dof_efforts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "mi_set_dof_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                    C.c_void_p]),

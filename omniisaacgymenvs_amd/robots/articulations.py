@@ -250,6 +250,46 @@ class ArticulationView:
                                                out.data_ptr(), self.stream()), "mi_get_link_jacobian")
         return out
 
+    # ---- dynamics view (include/mi_sim.h mi_get_dynamics): M u' + c + g = tau ----
+    # One launch fills the view's own output buffers, allocated on the first call and reused, so
+    # later calls allocate nothing and can sit inside torch.cuda.graph (call once before
+    # capturing). clone=False hands out the buffer itself, which the next call overwrites;
+    # ``indices`` selects rows after the launch, as the state getters do.
+    def _dynamics(self, M: bool, cor: bool, grav: bool):
+        if self.handle is None:
+            raise RuntimeError("the articulation view is not initialized")
+        buf = getattr(self, "_dyn_buf", None)
+        if buf is None:
+            nv = self.num_gen_vel
+            buf = self._dyn_buf = (self._empty(self.count, nv, nv), self._empty(self.count, nv),
+                                   self._empty(self.count, nv))
+        rc = self._lib.mi_get_dynamics(self.handle, buf[0].data_ptr() if M else None,
+                                       buf[1].data_ptr() if cor else None,
+                                       buf[2].data_ptr() if grav else None, self.stream())
+        if rc:
+            N.check(rc, "mi_get_dynamics")
+        return buf
+
+    def get_mass_matrices(self, indices=None, clone: bool = True) -> torch.Tensor:
+        """[count, nv, nv] joint-space inertia of the rigid-body tree (no armature, no damping:
+        get_armatures / get_joint_dampings), rows and columns the generalized velocity."""
+        return self._out(self._dynamics(True, False, False)[0], indices, clone)
+
+    def get_coriolis_and_centrifugal_forces(self, indices=None, clone: bool = True) -> torch.Tensor:
+        """[count, nv] velocity-product forces c(q, u): the force that holds u' = 0 at gravity 0.
+        Neither joint damping nor the per-link angular damping is part of it."""
+        return self._out(self._dynamics(False, True, False)[1], indices, clone)
+
+    def get_generalized_gravity_forces(self, indices=None, clone: bool = True) -> torch.Tensor:
+        """[count, nv] generalized gravity forces g(q), with each env's own gravity when
+        set_env_gravity gave it one: ``set_joint_efforts(g[:, -num_dof:])`` holds the joints
+        against gravity."""
+        return self._out(self._dynamics(False, False, True)[2], indices, clone)
+
+    def get_dynamics(self, indices=None, clone: bool = True):
+        """(M, c, g) of the three getters above from one launch."""
+        return tuple(self._out(t, indices, clone) for t in self._dynamics(True, True, True))
+
     # ---- setters (indices: env ids, rows of the value tensors align with them) ----
     @staticmethod
     def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
