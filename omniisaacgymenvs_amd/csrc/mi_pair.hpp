@@ -86,22 +86,28 @@ MI_D int pmax(int v) { return max(__builtin_amdgcn_readlane(v, 0), __builtin_amd
 // sum over each 32-lane half, returned to every lane of the half
 MI_D float psum(float v) { return pbc(half_sums(v), 31); }
 
-// in-register tree LTDL (ct_ltdl) with per-half broadcasts
+// in-register tree LTDL (ct_ltdl: the same statement, see there for what is kept exact and what
+// is left as junk) with per-half broadcasts; lane c of each half returns 1 / D_c. The junk above
+// the diagonal differs per column and per env, but stays in its own half's lanes (pbcc reads the
+// lane's own half) and in entries nothing reads
 template <class T>
-MI_D void ct_ltdl_pair(int lane, float (&Mc)[T::nvc]) {
+MI_D float ct_ltdl_pair(int lane, float (&Mc)[T::nvc]) {
+    float dvec = 1.0f;
     sfor_down<0, T::nv>([&](auto K) {
         constexpr int k = K;
         // no scheduling barrier per pivot: pivots of different limbs overlap (0.1262 -> 0.1254
         // ms A/B; a barrier every 2 or 4 pivots the same; no spills either way)
         const int ln = lane_here(lane);
         const float inv = __builtin_amdgcn_rcpf(pbcc<k>(Mc[k]));
+        const float t = Mc[k] * inv;
         sfor<T::dof.anc_start[k], T::dof.anc_start[k + 1]>([&](auto A) {
             constexpr int ii = T::dof.anc[A];
-            const float s = pbcc<ii>(Mc[k]) * inv;
-            if (ln <= ii) Mc[ii] -= s * Mc[k];
+            Mc[ii] -= pbcc<ii>(t) * Mc[k];
         });
-        if (ln < k) Mc[k] = Mc[k] * inv;
+        Mc[k] = t;
+        dvec = ln == k ? inv : dvec;
     });
+    return dvec;
 }
 
 // Per-DOF loop over the motion subspaces S_c (6 floats per DOF in LDS, uniform per half) and,
@@ -465,9 +471,8 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
     // ---- P4: register LTDL (lane = column), factor published to LDS
     float Mc[TP::nvc];
     ct_load_columns<TP>(Mx, lane, Mc);
-    ct_ltdl_pair<TP>(lane, Mc);
+    const float dvec = ct_ltdl_pair<TP>(lane, Mc);
     STAMP(5);
-    const float dvec = ct_dinv<TP>(lane, Mc);
     {
         const int dj = lane < nr ? lane : __builtin_popcount(mc.mask(lane < nv ? lane - nr + 1 : 0)) - 1;
         ct_publish_factor<TP>(lane, dj, Mc, dvec, sm + t.s_L);

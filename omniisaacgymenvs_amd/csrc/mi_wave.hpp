@@ -269,7 +269,7 @@ MI_D void tree_solve_lds(const WaveTabs& t, const float* Mx, const float* Dinv, 
 
 // ---- compile-time-topology (CT) tree kernels --------------------------------------------
 // Layout: lane c holds column c of M~ in Mc[0..nv-1] (Mc[r] = M~[r][c], lower triangle and
-// tree pattern only; every other entry exactly 0). Factor entries are broadcast with
+// tree pattern only; every other entry exactly 0 as loaded). Factor entries are broadcast with
 // v_readlane at compile-time (register, lane) pairs, so no LDS or barrier is involved.
 // Arithmetic is operation-for-operation that of the runtime-table path above.
 
@@ -281,20 +281,42 @@ MI_D int lane_here(int lane) {
     return lane;
 }
 
+// The rows lane c keeps are one word of a compile-time table (dof.col_rows[c]: c itself and its
+// descendants), read once; row r is then bit r of it spread over the word and and-ed onto the
+// loaded bits (v, or +0.0f as before): 2 VALU ops per row instead of a 64-bit shift, an and, a
+// compare and a select. Every entry of Mx is written in P3 (row k by lane k, all nv columns), so
+// no lane reads unwritten LDS; everything outside the kept pattern, the upper triangle included,
+// still starts at exactly 0 (the factorisation then leaves junk above the diagonal, see ct_ltdl).
 template <class T>
 MI_D void ct_load_columns(const float* Mx, int lane, float (&Mc)[T::nvc]) {
     const int c = lane < T::nv ? lane : 0;
+    const unsigned rows = lane < T::nv ? T::dof.col_rows[c] : 0u;
     sfor<0, T::nv>([&](auto R) {
         constexpr int r = R;
-        constexpr unsigned long long keep = (unsigned long long)T::dof.anc_mask[r] | (1ull << r);
-        const float v = Mx[r * T::nv + c];   // loaded by every lane, then selected: no branch
-        Mc[r] = ((keep >> lane_here(lane)) & 1ull) ? v : 0.0f;
+        const float v = Mx[r * T::nv + c];   // loaded by every lane, then masked: no branch
+        Mc[r] = __int_as_float(__float_as_int(v) & ((int)(rows << (31 - r)) >> 31));   // v_bfe_i32, v_and
     });
 }
 
-// in-register tree LTDL: M~ = L^T D L, L strictly below the diagonal, D on it
+// in-register tree LTDL: M~ = L^T D L. On return lane j holds L[i][j] in Mc[i] for every
+// descendant i of j, and the function's value in lane c is 1 / D_c (lanes >= nv: 1, unused).
+//
+// Only what is read later is kept exact; the rest of Mc is junk on return:
+//   * row k is scaled once per pivot, t = Mc[k] * inv in every lane, and the multiplier of
+//     ancestor ii is lane ii's t: the same single product of the same two floats as scaling the
+//     broadcast value, so the same bits. The update itself uses the unscaled Mc[k].
+//   * the update of Mc[ii] runs in every lane. Lane c <= ii reads Mc[k] of lane c < k (lower
+//     triangle), the broadcasts read lanes ii < k and k of row k, so no lower-triangle or diagonal
+//     entry ever depends on one above the diagonal; the lanes c > ii only collect the symmetric
+//     counterparts of the updates (finite wherever the factor is: products of lower-triangle
+//     entries; ct_load_columns starts them at 0), and nothing reads them.
+//   * t replaces Mc[k] in every lane, and 1 / D_k is taken from inv (the rcpf of the diagonal
+//     that a later pass used to redo) in lane k: after pivot k only the lanes j < k of Mc[k]
+//     are read again (ct_publish_factor and ct_solve read Mc[i] at ancestors j of i only).
+// lane_here serves the one lane compare left per pivot.
 template <class T>
-MI_D void ct_ltdl(int lane, float (&Mc)[T::nvc]) {
+MI_D float ct_ltdl(int lane, float (&Mc)[T::nvc]) {
+    float dvec = 1.0f;
     sfor_down<0, T::nv>([&](auto K) {
         constexpr int k = K;
         __builtin_amdgcn_sched_barrier(0);
@@ -302,21 +324,15 @@ MI_D void ct_ltdl(int lane, float (&Mc)[T::nvc]) {
         // hardware reciprocal (1 ulp) instead of the ~10-instruction IEEE division on the
         // factorisation's dependent chain
         const float inv = __builtin_amdgcn_rcpf(readlane(Mc[k], k));
+        const float t = Mc[k] * inv;
         sfor<T::dof.anc_start[k], T::dof.anc_start[k + 1]>([&](auto A) {
             constexpr int ii = T::dof.anc[A];
-            const float s = readlane(Mc[k], ii) * inv;
-            if (ln <= ii) Mc[ii] -= s * Mc[k];
+            Mc[ii] -= readlane(t, ii) * Mc[k];
         });
-        if (ln < k) Mc[k] = Mc[k] * inv;
+        Mc[k] = t;
+        dvec = ln == k ? inv : dvec;
     });
-}
-
-// lane c: 1 / D_c (lanes >= nv: unused)
-template <class T>
-MI_D float ct_dinv(int lane, const float (&Mc)[T::nvc]) {
-    float dg = 1.0f;
-    sfor<0, T::nv>([&](auto I) { dg = lane_here(lane) == I ? Mc[I] : dg; });
-    return __builtin_amdgcn_rcpf(dg);
+    return dvec;
 }
 
 template <class T>
@@ -733,8 +749,7 @@ MI_D void wave_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
     float dvec = 1.0f;    // CT path: lane c holds 1 / D_c
     if constexpr (TP::kCT) {
         ct_load_columns<TP>(Mx, lane, Mc);
-        ct_ltdl<TP>(lane, Mc);
-        dvec = ct_dinv<TP>(lane, Mc);
+        dvec = ct_ltdl<TP>(lane, Mc);
         const int dj = lane < nr ? lane : __builtin_popcount(mc.mask(lane < nv ? lane - nr + 1 : 0)) - 1;
         ct_publish_factor<TP>(lane, dj, Mc, dvec, sm + t.s_L);
     } else {
