@@ -862,6 +862,10 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
         // row's lambda over the sub-steps (lsum: u-bar = u* + W lsum / iters)
         [[maybe_unused]] const float sep = b;
         [[maybe_unused]] float ds = 0.0f, lsum = 0.0f;
+        // lam: this lane's own row's lambda of the current sweep, kept by the owner at its row
+        // step (mine there is the value the broadcast hands out, lamv[rr]); 0 at each sweep's
+        // start, so a row in a group never run keeps the 0 that lamv holds for it
+        float lam = 0.0f;
         for (int it = 0; it < p.iters + p.viters; ++it) {
             if constexpr (TP::kTgs)
                 b = (kd == 1 || kd == 2) ? 0.0f : row_bias(p, sep + ds, p.h, it < p.iters);
@@ -869,6 +873,7 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
             int nrow_it = nrows_max;
             asm volatile("" : "+s"(nrow_it));
             float lamn = 0.0f;
+            lam = 0.0f;
             sfor<0, RMAX>([&](auto RR) {   // fully unrolled: Ar / lamv stay register-indexed
                 constexpr int rr = RR;
                 // uniform, per group of four rows: rows past the count in the last group run as
@@ -900,16 +905,12 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
                     v += Ar[rr] * (ln - l0);
 #endif
                     lamv[rr] = ln;
+                    lam = lane_here(lane) == rr ? mine : lam;
                 }
             });
             if constexpr (TP::kTgs) {
-                if (it < p.iters) {   // the sub-step moves row r by h v_r; its lambda joins the sum
-                    ds += p.h * v;
-                    float lo = 0.0f;
-#pragma unroll
-                    for (int rr = 0; rr < RMAX; ++rr) lo = lane_here(lane) == rr ? lamv[rr] : lo;
-                    lsum += lo;
-                }
+                // the sub-step moves row r by h v_r; its lambda joins the sum
+                if (it < p.iters) { ds += p.h * v; lsum += lam; }
             }
         }
         STAMP(28);
@@ -937,12 +938,8 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
         if constexpr (TP::kTgs)   // the positions' velocity (sub-steps' mean), in the dead rhs
             if (lane < NV) sm[t.s_r + lane] = ub;
         wave_sync();
-        {   // reuse: lambda of row rr, written by lane rr (one select chain, one store)
-            float lo = 0.0f;
-#pragma unroll
-            for (int rr = 0; rr < RMAX; ++rr) lo = lane_here(lane) == rr ? lamv[rr] : lo;
-            if (lane < nrows) sm[t.s_ad + lane] = lo;
-        }
+        // reuse: lambda of row lane (the last sweep's), for the sensors of the final substep
+        if (store_state && lane < nrows) sm[t.s_ad + lane] = lam;
     } else if (nrows_max <= 64) {
 #ifndef MI_EXP_NO_WIDE
         // Wide Delassus (a half with 33..64 rows: 0.4 % of Humanoid substeps, but they set the
@@ -1234,7 +1231,7 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
             if (l64 < NV) smh[t.s_us + l64] = u;
             if constexpr (TP::kTgs)
                 if (l64 < NV) smh[t.s_r + l64] = ub;
-            if (l64 < nrh) smh[t.s_ad + l64] = lam;            // reuse: lambda of row l64
+            if (store_state && l64 < nrh) smh[t.s_ad + l64] = lam;   // reuse: lambda of row l64 (final substep's sensors)
             wave_sync();
             STAMP(11);
         }
@@ -1381,9 +1378,11 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
         if (lane < nv) us[lane] = u;
         if constexpr (TP::kTgs)   // the positions' velocity: the sub-steps' mean
             if (lane < nv) sm[t.s_r + lane] = usum / (float)p.iters;
-        if (lane < nrows) sm[t.s_ad + lane] = lam0;          // reuse: lambda of row lane
-        if (lane + 32 < nrows) sm[t.s_ad + lane + 32] = lam1;
-        for (int r = 64 + lane; r < nrows; r += 32) sm[t.s_ad + r] = gW[pair_sidx(r, WNV - 1)];
+        if (store_state) {   // reuse: lambda of row lane (final substep's sensors)
+            if (lane < nrows) sm[t.s_ad + lane] = lam0;
+            if (lane + 32 < nrows) sm[t.s_ad + lane + 32] = lam1;
+            for (int r = 64 + lane; r < nrows; r += 32) sm[t.s_ad + r] = gW[pair_sidx(r, WNV - 1)];
+        }
 #endif
     }
     wave_sync();
@@ -1394,7 +1393,10 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
     // (sensor, component) sums its component over the contacts in contact order — the serial
     // loop's terms and summation order (a non-touching contact adds a signed zero, which leaves
     // a sum started at +0 unchanged), without its per-contact latency chain.
-    if (t.sens_par) {
+    // Final substep only (store_state, wave-uniform): an earlier substep's wrenches, and the
+    // lambdas in s_ad they are built from, are overwritten by the next substep's P8 / row filing
+    // before anything reads them.
+    if (store_state && t.sens_par) {
         const int S = m.S;
         float* sb = sm + t.s_W;
         float* sums = sb + 6 * S * t.ncmax;
@@ -1455,7 +1457,7 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
                 sm[t.s_rb + 6 * si + 3 + q] = Tl[q];
             }
         }
-    } else if (lane < m.S) {
+    } else if (store_state && lane < m.S) {
         const int si = lane, l = (int)mc.sf(MS_LINK, si);
         float R[9], xs[3], F[3] = {0, 0, 0}, T[3] = {0, 0, 0};
 #pragma unroll

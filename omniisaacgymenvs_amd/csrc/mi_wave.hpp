@@ -1288,7 +1288,7 @@ MI_D void wave_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
             if (lane < NV) us[lane] = u;
             if constexpr (TP::kTgs)   // the positions' velocity, in the dead rhs
                 if (lane < NV) sm[t.s_r + lane] = ub;
-            if (lane < nrows) sm[t.s_ad + lane] = lam;           // reuse: lambda of row lane
+            if (store_state && lane < nrows) sm[t.s_ad + lane] = lam;   // reuse: lambda of row lane (final substep's sensors)
             lam_done = true;
         }
     }
@@ -1449,15 +1449,19 @@ MI_D void wave_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
         if (lane < nv) us[lane] = u;
         if constexpr (TP::kTgs)   // the positions' velocity: the sub-steps' mean
             if (lane < nv) sm[t.s_r + lane] = usum / (float)p.iters;
-        if (lane < nrows) sm[t.s_ad + lane] = lam0;          // reuse: lambda of row lane
-        if (lane + 64 < nrows) sm[t.s_ad + lane + 64] = lam1;
+        if (store_state) {   // reuse: lambda of row lane (final substep's sensors)
+            if (lane < nrows) sm[t.s_ad + lane] = lam0;
+            if (lane + 64 < nrows) sm[t.s_ad + lane + 64] = lam1;
+        }
     }
 #endif
     wave_sync();
 
     STAMP(11);  // P10 PGS
-    // ---- P11a: force sensors (lane s)
-    if (lane < m.S) {
+    // ---- P11a: force sensors (lane s). Final substep only (store_state, wave-uniform): an earlier
+    // substep's wrenches, and the lambdas in s_ad they are built from, are overwritten by the next
+    // substep's P8 / row filing before anything reads them.
+    if (store_state && lane < m.S) {
         const int si = lane, l = (int)mc.sf(MS_LINK, si);
         float R[9], xs[3], F[3] = {0, 0, 0}, T[3] = {0, 0, 0};
 #pragma unroll

@@ -37,6 +37,8 @@ MI355X-first execution:
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import math
 import os
 import time
@@ -49,6 +51,23 @@ import torch.nn as nn
 
 from . import ops
 from .models import ModelA2CContinuousLogStd, RunningMeanStd
+
+
+@contextlib.contextmanager
+def _no_gc_during_capture():
+    """Stream capture with Python's cyclic collector held off. A collection that lands inside a
+    capture may free dead cycles that own device memory or library handles (an env that was
+    dropped without close(), an older graph's pool): the hipFree invalidates the capture
+    (hipErrorStreamCaptureInvalidated at the next launch). torch.cuda.graph no longer collects on
+    entry, so: collect once before the capture, none during it."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 def _f(x) -> float:
@@ -486,7 +505,7 @@ class A2CAgent:
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
         try:
-            with torch.cuda.graph(g):
+            with _no_gc_during_capture(), torch.cuda.graph(g):
                 self._rollout_body()
         except Exception as e:  # noqa: BLE001 - fall back to eager launches, loudly
             print(f"[rlg] rollout graph capture failed ({e}); running the rollout eagerly")
@@ -606,14 +625,14 @@ class A2CAgent:
             torch.cuda.synchronize(self.device)
             if self.dp:
                 ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                with torch.cuda.graph(ga):   # records the launches without running them
+                with _no_gc_during_capture(), torch.cuda.graph(ga):   # records the launches without running them
                     self._mb_grad(i)
-                with torch.cuda.graph(gb, pool=ga.pool()):
+                with _no_gc_during_capture(), torch.cuda.graph(gb, pool=ga.pool()):
                     self._mb_apply(i)
                 g = (ga, gb)
             else:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with _no_gc_during_capture(), torch.cuda.graph(g):
                     self._minibatch_device(i)
             self.upd_graphs[key] = g
         if self.dp:
