@@ -145,25 +145,11 @@ MI_D void sdof_loop(const float* Ss, const float* R, F&& fn) {
 // (863 B/env) for +0.3 % kernel time (alternating A/B, profiles/r06/ab_areg/)
 #define MI_PAIR_WIDE_AREG 28
 #endif
-#ifndef MI_PAIR_WIDE_MFMA_HOIST
-#define MI_PAIR_WIDE_MFMA_HOIST 1   // MFMA set-up: all row blocks' J operands loaded before the tiles
-#endif
-#ifndef MI_PAIR_WIDE_MFMA
-#define MI_PAIR_WIDE_MFMA 0   // wide Delassus set-up as f32 MFMA tiles through the wave's scratch (0: per-lane FMA rows;
-                                // A/B round 5: MFMA 0.1371 ms, operands hoisted 0.1272, FMA 0.1245)
-#endif
 // the wave's global scratch of the wide sweeps, rows of 64 lanes of f32 per wave (N / 2 waves):
-// with the MFMA set-up the whole 64 x 64 Delassus block plus J^T (up to 32 DOF columns); else
 // the rows AREG..63 the sweeps stream (the rest stay in registers)
-constexpr int kWideScratchRows = MI_PAIR_WIDE_MFMA ? 64 + 32 : 64 - MI_PAIR_WIDE_AREG;
+constexpr int kWideScratchRows = 64 - MI_PAIR_WIDE_AREG;
 #ifndef MI_PAIR_WIDE_AP
 #define MI_PAIR_WIDE_AP 8   // Delassus rows streamed ahead of the wide sweeps' chain
-#endif
-#ifndef MI_PAIR_SWEEP_FMA
-#define MI_PAIR_SWEEP_FMA 1   // PGS row step as two FMAs around the projection (0: l0 + (b - v) / A_rr, v + A (ln - l0))
-#endif
-#ifndef MI_PAIR_WIDE_UPF
-#define MI_PAIR_WIDE_UPF 1   // wide u update: next group's W column loaded ahead (0: in order)
 #endif
 #ifndef MI_PAIR_LIM_NEAR
 #define MI_PAIR_LIM_NEAR 0.05f   // rad / m: a joint this close to a limit is speculated on first
@@ -182,41 +168,18 @@ constexpr int kWideScratchRows = MI_PAIR_WIDE_MFMA ? 64 + 32 : 64 - MI_PAIR_WIDE
 // x, y, z: the P1 set-up below), so their dot product is one component of f (what dot6 with a
 // unit vector returns, up to the sign of a zero); the joint DOFs' from S_c in LDS
 typedef float pv2 __attribute__((ext_vector_type(2)));
-// dot6 as two packed-FP32 chains (even / odd terms, v_pk_mul + 2 v_pk_fma + one add: 4 VALU
-// ops instead of 6); the summation order is (a0 b0 + a2 b2 + a4 b4) + (a1 b1 + a3 b3 + a5 b5)
-MI_D float dot6p(const float (&a)[6], const float (&b)[6]) {
-    pv2 p = pv2{a[0], a[1]} * pv2{b[0], b[1]};
-    p = __builtin_elementwise_fma(pv2{a[2], a[3]}, pv2{b[2], b[3]}, p);
-    p = __builtin_elementwise_fma(pv2{a[4], a[5]}, pv2{b[4], b[5]}, p);
-    return p.x + p.y;
-}
-// J_r . u over the NV DOFs (u in LDS, uniform per half) as two packed-FP32 chains (even / odd
-// DOFs), then their sum: the narrow and the wide PGS form v_r the same way
+// J_r . u over the NV DOFs (u in LDS, uniform per half), in DOF order: the narrow and the wide
+// PGS form v_r the same way
 template <int NV, int NVC>
 MI_D float pk_jdot(const float (&J)[NVC], const float* u) {
-#if MI_PK_DOT
-    pv2 p = {0.0f, 0.0f};
-    sfor<0, NV / 2>([&](auto H) {
-        constexpr int c = 2 * H;
-        p = __builtin_elementwise_fma(pv2{J[c], J[c + 1]}, pv2{u[c], u[c + 1]}, p);
-    });
-    float v = p.x + p.y;
-    if constexpr (NV % 2) v += J[NV - 1] * u[NV - 1];
-    return v;
-#else
     float v = 0.0f;
     sfor<0, NV>([&](auto C) { v += J[C] * u[C]; });
     return v;
-#endif
 }
 template <class TP, int c>
 MI_D float sdot(const float (&sv)[6], const float (&f)[6]) {
     if constexpr (TP::nr == 6 && c < 6) return f[c < 3 ? 3 + c : c - 3];
-#if MI_PK_DOT
-    else return dot6p(sv, f);
-#else
     else return dot6(sv, f);
-#endif
 }
 constexpr int sdof_first_loaded(int nr) { return nr == 6 ? 6 : 0; }
 
@@ -261,12 +224,6 @@ MI_D lds_cf lds_ptr(const float* p) { return (lds_cf)p; }
 // wave) and the u update's four rows of the lane's DOF — instead of four ds_read_b32.
 // w_rows_lds is a multiple of 4 (host), so a group is wholly in LDS or wholly in the slab.
 typedef float pv4 __attribute__((ext_vector_type(4)));
-#ifndef MI_PK_FMA
-#define MI_PK_FMA 1   // Delassus set-up on packed FP32 FMAs (v_pk_fma_f32)
-#endif
-#ifndef MI_PK_DOT
-#define MI_PK_DOT 1   // S_c . f (J rows, CRBA columns) as two packed-FP32 chains
-#endif
 typedef const pv4 __attribute__((address_space(3)))* lds_cf4;
 MI_D int pw_idx(int r, int c, int nv) { return (r & ~3) * nv + 4 * c + (r & 3); }
 // The env's global W slab (rows >= w_rows_lds, up to MI_MAX_ROWS) uses the same 4-row groups,
@@ -311,7 +268,6 @@ MI_D WSrc make_wsrc(const WaveTabs& t, const float* sm, glb_cf gW) {
 template <class TP, int PD, bool kLds>
 MI_D void pair_dgroup_w(const WSrc& ws, int g0, int n, const float (&Jr)[TP::nvc], float (&a)[4]) {
     constexpr int NV = TP::nv, NB = PD + 1;
-#if MI_PK_FMA
     // two rows' chains per v_pk_fma_f32 (the same fused multiply-add per element, half the
     // VALU instructions)
     pv2 a01 = {0.0f, 0.0f}, a23 = {0.0f, 0.0f};
@@ -320,15 +276,6 @@ MI_D void pair_dgroup_w(const WSrc& ws, int g0, int n, const float (&Jr)[TP::nvc
         a01 = __builtin_elementwise_fma(j, w.xy, a01);
         a23 = __builtin_elementwise_fma(j, w.zw, a23);
     };
-#else
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-    auto acc = [&](auto C, const pv4& w) {
-        a0 += Jr[C] * w.x;
-        a1 += Jr[C] * w.y;
-        a2 += Jr[C] * w.z;
-        a3 += Jr[C] * w.w;
-    };
-#endif
     if (kLds || g0 + 3 < ws.nl) {
         const lds_cf4 W = (lds_cf4)(ws.W + g0 * NV);
         pv4 wb[NB];
@@ -348,9 +295,7 @@ MI_D void pair_dgroup_w(const WSrc& ws, int g0, int n, const float (&Jr)[TP::nvc
             acc(C, wb[c % NB]);
         });
     }
-#if MI_PK_FMA
     const float a0 = a01.x, a1 = a01.y, a2 = a23.x, a3 = a23.y;
-#endif
     a[0] = g0 < n ? a0 : 0.0f;
     a[1] = g0 + 1 < n ? a1 : 0.0f;
     a[2] = g0 + 2 < n ? a2 : 0.0f;
@@ -887,23 +832,15 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
                     const float l0 = lamv[rr];
                     const bool fric = kd == 1 || kd == 2;
                     const float lim = mu * lamn;
-#if MI_PAIR_SWEEP_FMA
                     // x = (l0 + b / A_rr) - v / A_rr and v + A (ln - l0) = (v - A l0) + A ln: the
                     // l0 terms come off the chain, which is then fma -> med3 -> broadcast -> fma
                     const float x = __builtin_fmaf(-v, ia, __builtin_fmaf(b, ia, l0));
-#else
-                    const float x = l0 + (b - v) * ia;
-#endif
                     // one med3: max(., lo) then, for friction, min(., lim) (lo <= hi: lamn >= 0)
                     const float mine = __builtin_amdgcn_fmed3f(x, fric ? -lim : 0.0f,
                                                                fric ? lim : __builtin_huge_valf());
                     const float ln = pbcc<rr>(mine);
                     if constexpr (rr % 3 == 0) lamn = rr < nnorm ? ln : lamn;
-#if MI_PAIR_SWEEP_FMA
                     v = __builtin_fmaf(Ar[rr], ln, __builtin_fmaf(-Ar[rr], l0, v));
-#else
-                    v += Ar[rr] * (ln - l0);
-#endif
                     lamv[rr] = ln;
                     lam = lane_here(lane) == rr ? mine : lam;
                 }
@@ -958,11 +895,11 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
         const int kc = l64 < NV ? l64 : 0;
         // this wave's scratch (its slot over the launch: the same for both halves), addressed through a buffer
         // resource: one lane offset register for every row (Delassus row s at soffset 256 (s -
-        // A0), A0 = 0 with the MFMA set-up (all 64 rows there), else AR); loads past the record
+        // A0), A0 = AR: the scratch holds the streamed rows only); loads past the record
         // range (prefetch beyond the last row) return 0
         const int wv = __builtin_amdgcn_readfirstlane(wv_);   // the wave's slot (pairs may be permuted)
         constexpr int WR = kWideScratchRows > 0 ? kWideScratchRows : 1;
-        constexpr int A0 = MI_PAIR_WIDE_MFMA ? 0 : AR;
+        constexpr int A0 = AR;
         const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(
             (void*)(t.g_wa + (size_t)wv * (WR * 64)), (short)0, WR * 64 * (int)sizeof(float), 0x00020000);
         const int avo = l64 * (int)sizeof(float);
@@ -993,93 +930,6 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
             float v = pk_jdot<NV>(Jr, ush);
             STAMP(30);
             float Ar[AR > 0 ? AR : 1];
-#if MI_PAIR_WIDE_MFMA
-            {
-                // A = J W^T as v_mfma_f32_16x16x4f32 tiles (A[m][k] at lane m + 16 k, B[k][n] at
-                // lane n + 16 k, D[4 (l >> 4) + i][l & 15] in register i): J^T goes to the scratch
-                // (column c at row 64 + c, lane = constraint row; rows past the env's count and the
-                // padding columns 0), each 16-row block of J comes back in the A-operand layout, W
-                // in the B-operand layout straight from LDS / the slab. A tile's D is stored as
-                // scratch rows 16 R + 4 (l >> 4) + i, lanes 16 S + (l & 15): row s then holds
-                // A[s][r] at lane r (A symmetric), the layout the sweeps read. Every 16-lane
-                // column block is written (rows past the count come out 0), row blocks up to the
-                // count only (the sweeps read no further). Sums in the MFMA's order, not DOF order.
-                constexpr int KP = (NV + 3) & ~3, KC = KP / 4;
-                static_assert(KP <= 32, "wide scratch holds 32 J^T columns");
-                sfor<0, KP>([&](auto C) {
-                    constexpr int c = C;
-                    float jv = 0.0f;
-                    if constexpr (c < NV) jv = l64 < nrh ? Jr[c] : 0.0f;
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, jv), ars, avo, (64 + c) * 256, 0);
-                });
-                wave_sync();   // J^T stored before the A-operand loads read it back
-                const int lr = l64 & 15, lk = l64 >> 4;
-                const int jvo = ((64 + lk) * 64 + lr) * (int)sizeof(float);
-                const int dvo = (4 * lk * 64 + lr) * (int)sizeof(float);
-#if MI_PAIR_WIDE_MFMA_HOIST
-                // every row block's A operands in flight at once (one L2 round trip, not one per tile)
-                float jall[4][KC];
-                sfor<0, 4>([&](auto R) {
-                    sfor<0, KC>([&](auto K) {
-                        jall[R][K] = 16 * R < nrh ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                                                  ars, jvo, (K * 256 + 16 * R) * 4, 0))
-                                                  : 0.0f;
-                    });
-                });
-#endif
-                sfor<0, 4>([&](auto S) {   // column block: lanes 16 S .. 16 S + 15
-                    const int s = 16 * S + lr;
-                    float wb[KC];
-                    sfor<0, KC>([&](auto K) {
-                        const int c = 4 * K + lk;
-                        float w = 0.0f;
-                        if (16 * S < nrh && s < nrh && c < NV) {
-                            if (s < t.w_rows_lds) w = lds_ptr(smh)[t.s_W + pw_idx(s, c, NV)];
-                            else w = gWh[pair_sidx(s, c)];
-                        }
-                        wb[K] = w;
-                    });
-                    sfor<0, 4>([&](auto R) {   // row block: scratch rows 16 R .. 16 R + 15
-                        if (16 * R < nrh) {
-                            pv4 d = {0.0f, 0.0f, 0.0f, 0.0f};
-                            sfor<0, KC>([&](auto K) {
-#if MI_PAIR_WIDE_MFMA_HOIST
-                                const float ja = jall[R][K];
-#else
-                                const float ja = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                                               ars, jvo, (K * 256 + 16 * R) * 4, 0));
-#endif
-                                d = __builtin_amdgcn_mfma_f32_16x16x4f32(ja, wb[K], d, 0, 0, 0);
-                            });
-                            // D moved to VGPRs first: stored straight from the accumulator tuple, this
-                            // compiler (ROCm 7.2) emits four stores of its first register
-                            // (tools/mfma_wide_check.hip)
-                            float o4[4] = {d.x, d.y, d.z, d.w};
-                            asm volatile("" : "+v"(o4[0]), "+v"(o4[1]), "+v"(o4[2]), "+v"(o4[3]));
-#pragma unroll
-                            for (int q = 0; q < 4; ++q)
-                                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o4[q]), ars, dvo,
-                                                                      ((16 * R + q) * 64 + 16 * S) * 4, 0);
-                        }
-                    });
-                });
-                wave_sync();   // the tiles stored before the rows are read back lane = row
-                if constexpr (AR > 0) {
-                    sfor<0, AR / 4>([&](auto G) {
-                        constexpr int g0 = 4 * G;
-                        if (g0 < nrh) {
-#pragma unroll
-                            for (int q = 0; q < 4; ++q)
-                                Ar[g0 + q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                                           ars, avo, (g0 + q) * 256, 0));
-                        } else {
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) Ar[g0 + q] = 0.0f;
-                        }
-                    });
-                }
-            }
-#else
             sfor<0, 16>([&](auto G) {
                 constexpr int g0 = 4 * G;
                 float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -1098,7 +948,6 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
                 if constexpr (g0 < AR) { Ar[g0] = a[0]; Ar[g0 + 1] = a[1]; Ar[g0 + 2] = a[2]; Ar[g0 + 3] = a[3]; }
             });
             if constexpr (AR < 64) wave_sync();
-#endif
             STAMP(27);
             float b = 0.0f, ia = 0.0f, lam = 0.0f;    // ia 0: a dead row keeps its lambda 0
             int kd = 0;
@@ -1118,11 +967,9 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
                 int nrow_it = nrh;
                 asm volatile("" : "+s"(nrow_it));
                 float lamn = 0.0f;
-#if MI_PAIR_SWEEP_FMA
                 const float tl = __builtin_fmaf(b, ia, lam);   // lane = row: lam changes at its own row only
                 float muv = muh, lov = 0.0f, hiv = 0.0f;       // mu in a VGPR: mu lambda_n in one v_mul
                 asm volatile("" : "+v"(muv));
-#endif
                 // rows rr .. rr + PA - 1 of A in flight. The scratch is NOT zeroed (no memset at
                 // creation): correctness rests on the invariant that the set-up writes every row
                 // of every group of four it processes ((rr & ~3) < nrh, the sweeps' condition),
@@ -1152,7 +999,6 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
                             arr = ab[(rr - AR) % PA];
                             if constexpr (rr + PA < 64) ab[(rr - AR) % PA] = ald(rr + PA);
                         }
-#if MI_PAIR_SWEEP_FMA
                         // the narrow sweeps' arithmetic (bit for bit: an env's result does not
                         // depend on the path its partner sends the wave down): the new lambda
                         // and the row's old one leave the owner by v_readlane (the old one off
@@ -1173,20 +1019,6 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
                         v = __builtin_fmaf(arr, ln, __builtin_fmaf(-arr, l0, v));
                         asm("v_writelane_b32 %0, %1, %2" : "+v"(lam) : "s"(ln), "i"(rr));
                         (void)lw;
-#else
-                        const bool fric = kd == 1 || kd == 2;
-                        const float lim = muh * lamn;
-                        const float mine = __builtin_amdgcn_fmed3f(lam + (b - v) * ia, fric ? -lim : 0.0f,
-                                                                   fric ? lim : __builtin_huge_valf());
-                        // the owner forms the lambda change itself (mine - lam there is exactly
-                        // ln - l0) and keeps mine as its lambda: one v_readlane per row (two for
-                        // the normal rows, whose lambda bounds the next two), no SGPR pair to
-                        // move back for the subtraction
-                        const float dl = readlane(mine - lam, rr);
-                        if constexpr (rr % 3 == 0) lamn = rr < nnh ? readlane(mine, rr) : lamn;
-                        v += arr * dl;
-                        lam = lw == rr ? mine : lam;
-#endif
                     }
                 });
                 if constexpr (TP::kTgs) {
@@ -1198,24 +1030,18 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
             float u = ush[kc];
             [[maybe_unused]] float ub = u;
             [[maybe_unused]] const float lbar = lsum / (float)p.iters;
-#if MI_PAIR_WIDE_UPF
             // the next group's W column is loaded before this group's FMAs (rows past the LDS
             // ones come from the slab: one L2 round trip per group on the chain otherwise)
             float wn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             pair_wcol_w<(3 < TP::kLamRows)>(wsh, 0, kc, NV, wn);
-#endif
             sfor<0, 16>([&](auto G) {
                 constexpr int g0 = 4 * G;
                 if (g0 < nrh) {
                     float wq[4];
-#if MI_PAIR_WIDE_UPF
 #pragma unroll
                     for (int q = 0; q < 4; ++q) wq[q] = wn[q];
                     if constexpr (g0 + 4 < 64)
                         if (g0 + 4 < nrh) pair_wcol_w<(g0 + 7 < TP::kLamRows)>(wsh, g0 + 4, kc, NV, wn);
-#else
-                    pair_wcol_w<(g0 + 3 < TP::kLamRows)>(wsh, g0, kc, NV, wq);
-#endif
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const float lq = readlane(lam, g0 + q);

@@ -136,6 +136,18 @@ static int upload(mi_sim* s, const T* host, size_t count, const T** out) {
 
 static inline dim3 grid_for(const mi_sim* s, int n) { return dim3((n + s->block - 1) / s->block); }
 
+// The one launch path of the kernels that can be timed: with an event pair (timed_launch) the
+// events ride on the kernel's own dispatch (hipExtLaunchKernelGGL), without one it is a plain
+// launch (hipLaunchKernelGGL: the only kind a capturing stream takes). One argument per kernel
+// parameter, converted to the parameter's type.
+template <typename... P, typename... A>
+static void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                   hipEvent_t ev0, hipEvent_t ev1, A... args) {
+    static_assert(sizeof...(P) == sizeof...(A), "one argument per kernel parameter");
+    if (ev0) hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, stream, ev0, ev1, 0, (P)args...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, stream, (P)args...);
+}
+
 // ---------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------
@@ -229,130 +241,75 @@ __global__ void k_post_step(DevModel m, DevState st, DevTask tp, const float* ac
 }
 
 // RLTask.post_physics_step for the locomotion tasks on the per-env record layout (fs = 1,
-// es = record floats): TE envs per 64-lane workgroup, HBM-streaming. The block's records and
-// action rows are contiguous in HBM: loaded with coalesced float4 reads into padded LDS rows;
-// lanes < TE then run the same per-env task math as k_post_step (loco_obs_env / loco_reward /
-// loco_done) on an LDS view of their env. STAGE: the obs rows go through an LDS tile and leave
-// as coalesced float4 stores (the [N, O] rows of TE consecutive envs are one contiguous span);
-// otherwise each lane stores its own row.
-MI_D void tile_load(const float* __restrict__ src, int count, float* dst, int row, int pad) {
-    // count floats (a multiple of row) from src into dst rows of `pad` floats
-    const int lane = threadIdx.x;
-    if ((((uintptr_t)src) & 15) == 0 && (row & 3) == 0) {
-        const float4* s4 = (const float4*)src;
-        for (int k = lane; k < count / 4; k += 64) {
-            const float4 v = s4[k];
-            const int f = 4 * k, e = f / row, c = f - e * row;
-            float* d = dst + e * pad + c;
-            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        }
-    } else {
-        for (int k = lane; k < count; k += 64) {
-            const int e = k / row;
-            dst[e * pad + (k - e * row)] = src[k];
-        }
-    }
-}
-
-template <int TE, bool STAGE>
+// es = record floats): 32 envs per 64-lane workgroup, HBM-streaming. The block's records are
+// contiguous in HBM: loaded with coalesced float4 reads into padded LDS rows; the lanes then run
+// the same per-env task math as k_post_step (loco_obs_* / loco_reward_* / loco_done) on an LDS
+// view of their env. The obs rows go through an LDS tile and leave as coalesced float4 stores (the
+// [N, O] rows of 32 consecutive envs are one contiguous span).
+constexpr int kPostTileEnvs = 32;
 __global__ __launch_bounds__(64) void k_loco_post_tiled(DevModel m, DevState st, DevTask tp,
                                                         const float* __restrict__ actions,
                                                         float* obs, float* rew, int64_t* reset_buf,
                                                         int64_t* progress_buf, float* pot,
                                                         float* prev) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
+    constexpr int TE = kPostTileEnvs;
     const int lane = threadIdx.x, e0 = blockIdx.x * TE;
     const int n = min(TE, st.N - e0);
     const int O = tp.O, A = tp.A;
-    if (TE == 32 && STAGE) {
-        // compact tile: each record's used fields only (root 13, q, qd: the float4s up to the end
-        // of qd, so the efforts line is never fetched) and the env's sensor wrenches from their
-        // own array; actions read in place
-        const int D = m.D, S = m.S;
-        const int k0 = 13 + 2 * D, ne4 = (k0 + 3) >> 2, ns = 6 * S, PC = (k0 + ns) | 1;   // odd row stride: no LDS bank aliasing across envs
-        float* srec = sm;
-        float* sobs = sm + TE * PC;
-        float* sterm = sobs + TE * O;                          // [TE][3] sums
-        {
-            const float4* s4 = (const float4*)(st.root_pos + (size_t)e0 * st.es);
-            for (int k = lane; k < n * ne4; k += 64) {         // es % 4 == 0 (whole lines)
-                const int e = k / ne4, c4 = k - e * ne4;
-                const float4 v4 = s4[e * (st.es >> 2) + c4];
-                const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int c = 4 * c4 + q;
-                    if (c < k0) srec[e * PC + c] = vv[q];
-                }
-            }
-            for (int k = lane; k < n * ns; k += 64) {
-                const int e = k / ns, c = k - e * ns;
-                srec[e * PC + k0 + c] = st.sens[ssx(st, c, e0 + e)];
-            }
-        }
-        __syncthreads();
-        DevState v = st;                    // the block's envs, viewed in LDS
-        v.fs = 1; v.es = PC;
-        v.root_pos = srec; v.root_quat = srec + 3; v.root_vel = srec + 7;
-        v.q = srec + 13; v.qd = srec + 13 + D; v.sens = srec + k0;
-        v.sfs = 1; v.ses = PC;
-        // split by lane halves: lanes 0..31 the root-frame block of env `lane`, lanes 32..63 the
-        // per-DOF / sensor block and the reward's DOF-order sums of env `lane - 32`
-        const int e = lane & 31;
-        float* R = sobs + (size_t)e * O;
-        if (e < n) {
-            if (lane < 32) {
-                loco_obs_root(v, tp, e, R, pot + e0, prev + e0);
-            } else {
-                loco_obs_dof(m, v, tp, e, actions + (size_t)(e0 + e) * A, INFINITY, R);
-                const LocoTerms lt = loco_reward_terms(tp, m.D, R, R + 12 + 2 * m.D + 6 * m.S);
-                sterm[3 * e] = lt.limit_cost; sterm[3 * e + 1] = lt.act_cost; sterm[3 * e + 2] = lt.elec;
-            }
-        }
-        __syncthreads();
-        if (lane < n) {
-            const int i = e0 + lane;
-            const LocoTerms lt{sterm[3 * lane], sterm[3 * lane + 1], sterm[3 * lane + 2]};
-            const int64_t progress = progress_buf[i] + 1;               // rl_task.py:242
-            rew[i] = loco_reward_total(tp, R[0], R[10], R[11], pot[i], prev[i], lt);
-            reset_buf[i] = nan_guard(st, i, loco_done(tp, R[0], reset_buf[i], progress));
-            progress_buf[i] = progress;
-        }
-        __syncthreads();
-        float* dst = obs + (size_t)e0 * O;
-        const int cnt = n * O;
-        if ((((uintptr_t)dst) & 15) == 0 && (cnt & 3) == 0) {
-            for (int k = lane; k < cnt / 4; k += 64)
-                ((float4*)dst)[k] = ((const float4*)sobs)[k];   // sobs 16-B aligned: ds_read_b128
-        } else {
-            for (int k = lane; k < cnt; k += 64) dst[k] = sobs[k];
-        }
-        return;
-    }
-    const int P = st.es + 1, AP = A + 1;
+    // compact tile: each record's used fields only (root 13, q, qd: the float4s up to the end
+    // of qd, so the efforts line is never fetched) and the env's sensor wrenches from their
+    // own array; actions read in place
+    const int D = m.D, S = m.S;
+    const int k0 = 13 + 2 * D, ne4 = (k0 + 3) >> 2, ns = 6 * S, PC = (k0 + ns) | 1;   // odd row stride: no LDS bank aliasing across envs
     float* srec = sm;
-    float* sact = sm + TE * P;
-    float* sobs = sact + TE * AP;
-    tile_load(st.root_pos + (size_t)e0 * st.es, n * st.es, srec, st.es, P);
-    tile_load(actions + (size_t)e0 * A, n * A, sact, A, AP);
+    float* sobs = sm + TE * PC;
+    float* sterm = sobs + TE * O;                          // [TE][3] sums
+    {
+        const float4* s4 = (const float4*)(st.root_pos + (size_t)e0 * st.es);
+        for (int k = lane; k < n * ne4; k += 64) {         // es % 4 == 0 (whole lines)
+            const int e = k / ne4, c4 = k - e * ne4;
+            const float4 v4 = s4[e * (st.es >> 2) + c4];
+            const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = 4 * c4 + q;
+                if (c < k0) srec[e * PC + c] = vv[q];
+            }
+        }
+        for (int k = lane; k < n * ns; k += 64) {
+            const int e = k / ns, c = k - e * ns;
+            srec[e * PC + k0 + c] = st.sens[ssx(st, c, e0 + e)];
+        }
+    }
     __syncthreads();
-    DevState v = st;                        // the block's envs, viewed in LDS
-    v.fs = 1; v.es = P;
-    v.root_pos = srec; v.root_quat = srec + (st.root_quat - st.root_pos);
-    v.root_vel = srec + (st.root_vel - st.root_pos);
-    v.q = srec + (st.q - st.root_pos); v.qd = srec + (st.qd - st.root_pos);
-    v.sens = st.sens + ssx(st, 0, e0);      // sensor wrenches read in place (their own array)
+    DevState v = st;                    // the block's envs, viewed in LDS
+    v.fs = 1; v.es = PC;
+    v.root_pos = srec; v.root_quat = srec + 3; v.root_vel = srec + 7;
+    v.q = srec + 13; v.qd = srec + 13 + D; v.sens = srec + k0;
+    v.sfs = 1; v.ses = PC;
+    // split by lane halves: lanes 0..31 the root-frame block of env `lane`, lanes 32..63 the
+    // per-DOF / sensor block and the reward's DOF-order sums of env `lane - 32`
+    const int e = lane & 31;
+    float* R = sobs + (size_t)e * O;
+    if (e < n) {
+        if (lane < 32) {
+            loco_obs_root(v, tp, e, R, pot + e0, prev + e0);
+        } else {
+            loco_obs_dof(m, v, tp, e, actions + (size_t)(e0 + e) * A, INFINITY, R);
+            const LocoTerms lt = loco_reward_terms(tp, m.D, R, R + 12 + 2 * m.D + 6 * m.S);
+            sterm[3 * e] = lt.limit_cost; sterm[3 * e + 1] = lt.act_cost; sterm[3 * e + 2] = lt.elec;
+        }
+    }
+    __syncthreads();
     if (lane < n) {
         const int i = e0 + lane;
-        float* R = STAGE ? sobs + (size_t)lane * O : obs + (size_t)i * O;
-        const int64_t progress = progress_buf[i] + 1;                   // rl_task.py:242
-        loco_obs_env(m, v, tp, lane, sact + lane * AP, INFINITY, R, pot + e0, prev + e0);
-        const float* ca = R + 12 + 2 * m.D + 6 * m.S;
-        rew[i] = loco_reward(tp, m.D, R, ca, pot[i], prev[i]);        // calculate_metrics
-        reset_buf[i] = nan_guard(st, i, loco_done(tp, R[0], reset_buf[i], progress));  // is_done
+        const LocoTerms lt{sterm[3 * lane], sterm[3 * lane + 1], sterm[3 * lane + 2]};
+        const int64_t progress = progress_buf[i] + 1;               // rl_task.py:242
+        rew[i] = loco_reward_total(tp, R[0], R[10], R[11], pot[i], prev[i], lt);
+        reset_buf[i] = nan_guard(st, i, loco_done(tp, R[0], reset_buf[i], progress));
         progress_buf[i] = progress;
     }
-    if (!STAGE) return;
     __syncthreads();
     float* dst = obs + (size_t)e0 * O;
     const int cnt = n * O;
@@ -364,21 +321,19 @@ __global__ __launch_bounds__(64) void k_loco_post_tiled(DevModel m, DevState st,
     }
 }
 
-static size_t post_tile_lds(int te, bool stage, int es, int A, int O, int D, int S) {
-    if (te == 32 && stage)   // compact record tile + obs tile + reward sums
-        return sizeof(float) * (size_t)(te * (13 + 2 * D + 6 * S + 1) + te * O + 3 * te);
-    return sizeof(float) * (size_t)(te * (es + 1) + te * (A + 1) + (stage ? te * O : 0));
+// compact record tile + obs tile + reward sums
+static size_t post_tile_lds(int O, int D, int S) {
+    constexpr int te = kPostTileEnvs;
+    return sizeof(float) * (size_t)(te * (13 + 2 * D + 6 * S + 1) + te * O + 3 * te);
 }
 
-// variant of the tiled post-step (MI_POST_TILE=32p|16p|64s|64d|32s|32d, read per launch so a
-// test can compare variants in one process; default 32p = k_loco_post_pipe with 32-env tiles,
-// 16p the same kernel with 16-env tiles)
+// kernel of the locomotion post-step (MI_POST_TILE=32p|16p|32s, read per launch so a test can
+// compare them in one process): 32p (default, and any other value) = k_loco_post_pipe with 32-env
+// tiles, 16p the same kernel with 16-env tiles, 32s = the one-tile kernel k_loco_post_tiled. The
+// values are the codes mi_task_post_kernel reports.
 static int post_tile_variant() {
     const char* e = getenv("MI_POST_TILE");
-    if (e && !strcmp(e, "64s")) return 0;
-    if (e && !strcmp(e, "64d")) return 1;
     if (e && !strcmp(e, "32s")) return 2;
-    if (e && !strcmp(e, "32d")) return 3;
     if (e && !strcmp(e, "16p")) return 6;
     return 4;   // 32p
 }
@@ -574,10 +529,10 @@ __device__ __forceinline__ float* wave_env_lds(const WaveTabs& t, float* smem) {
     return smem + (threadIdx.x >> 6) * t.env_stride;
 }
 
-// k_loco_post_tiled<32, true> with the HBM latency hidden behind the math: each workgroup walks
+// k_loco_post_tiled with the HBM latency hidden behind the math: each workgroup walks
 // the tiles t = blockIdx.x, + gridDim.x, ... (grid = resident workgroups) and, while it computes
 // tile t from LDS, holds the global loads of tile t + gridDim.x in registers (records, action
-// rows, per-env scalars). Same arithmetic and write order per env as k_loco_post_tiled<32, true>
+// rows, per-env scalars). Same arithmetic and write order per env as k_loco_post_tiled
 // (bit-identical outputs).
 // Data movement is whole float4s with wave-uniform trip counts and no per-element guards:
 //  - record tile in LDS: per env the record's first ne4 float4s (root, q, qd: the whole lines the
@@ -626,9 +581,6 @@ static size_t post_pipe_lds(int es, int A, int O, int D, int S, int te = 32) {
     return sizeof(float) * (size_t)(te * g.P + 4 + te * O + 2 * te + 4);
 }
 
-#ifndef MI_PIPE_ROT
-#define MI_PIPE_ROT 1   // rotated pipeline with fixed-count stores (0: loads consumed at the loop head)
-#endif
 // NO4: obs float4s per lane per tile (>= TE O / 256, host-checked).
 // TE envs per tile (32, or 16: half the LDS and prefetch registers per workgroup, so more
 // workgroups stay resident; lanes e + 16 then repeat env e's root / reward chains, writing nothing)
@@ -689,7 +641,6 @@ __global__ __launch_bounds__(64) void k_loco_post_pipe(const KParams* __restrict
     const float dof_hi = dof_lane ? kp->m.upper[dof_j + 1] : 1.0f;
     const int sen_pe = ns > 0 ? 64 / ns : 0, sen_le = ns > 0 ? lane / ns : 0, sen_c = lane - sen_le * ns;
     const bool sen_lane = ns > 0 && sen_le < sen_pe;
-#if MI_PIPE_ROT
     // Rotated pipeline: tile t + G's loads are issued after tile t's first barrier and moved
     // into LDS at the END of iteration t, after tile t's stores. Every memory op between the two
     // is an unconditional store of a fixed count (per-env outputs from all 64 lanes, NO4 obs
@@ -798,96 +749,6 @@ __global__ __launch_bounds__(64) void k_loco_post_pipe(const KParams* __restrict
 #undef MI_PIPE_STAGE
 #undef MI_PIPE_ISSUE
 }
-#else
-    int t = blockIdx.x;
-    if (t < ntiles) MI_PIPE_ISSUE(kp, t);
-    for (; t < ntiles; t += gridDim.x) {
-        const KParams* k = opaque_kp(kp_arg);
-        const int e0 = t * TE, n = min(TE, N - e0);
-        // registers -> LDS: records (float4 slots), actions into the obs rows' action columns
-#pragma unroll
-        for (int r = 0; r < NR4; ++r) {
-            const int kk = lane + 64 * r, e = div_small(kk, mag_ne);
-            srec4[kk < TE * g.ne4 ? e * g.P4 + (kk - e * g.ne4) : spare4] = rr[r];
-        }
-#pragma unroll
-        for (int r = 0; r < NS4; ++r) {
-            const int kk = lane + 64 * r, e = div_small(kk, mag_ns);
-            srec4[kk < TE * g.ns4 ? e * g.P4 + g.ne4 + (kk - e * g.ns4) : spare4] = rsn[r];
-        }
-#pragma unroll
-        for (int r = 0; r < MI_PIPE_A; ++r) {
-            const int kk = lane + 64 * r, e = div_small(kk, mag_a);
-            sobs[kk < TE * A ? e * O + ka + (kk - e * A) : trash_o] = ra[r];
-        }
-        const int64_t progress = pg + 1, rb = rs;          // rl_task.py:242
-        const int nflag = nf;
-        if (lane < TE) spot[lane] = pt;
-        __syncthreads();
-        if (t + (int)gridDim.x < ntiles) MI_PIPE_ISSUE(k, t + (int)gridDim.x);   // in flight during the math
-        // get_observations per-DOF and sensor entries (locomotion.py:226-228), the arithmetic of
-        // loco_obs_dof, on all 64 lanes: lane = (env slot, column), the column a lane constant
-        if (dof_lane) {
-            const float vs = k->tp.dof_vel_scale;
-            for (int e = dof_le; e < n; e += dof_pe) {
-                const float* r = srec + e * g.P;
-                float* o = sobs + e * O;
-                o[12 + dof_j] = ref_unscale(r[13 + dof_j], dof_lo, dof_hi);
-                o[12 + D + dof_j] = r[13 + D + dof_j] * vs;
-            }
-        }
-        if (sen_lane) {
-            const float cs = k->tp.contact_force_scale;
-            for (int e = sen_le; e < n; e += sen_pe)
-                sobs[e * O + 12 + 2 * D + sen_c] = srec[e * g.P + g.s0 + sen_c] * cs;
-        }
-        __syncthreads();
-        // root-frame block and the reward's DOF-order sums: env lane & (TE - 1) on both lane
-        // halves (the pair helpers see lane `pl`: with 16-env tiles lanes 16..31 / 48..63 act as
-        // 0..15 / 32..47 and write nothing)
-        const int pl = TE == 32 ? lane : ((lane & 15) | (lane & 32));
-        const bool pw = TE == 32 || (lane & 16) == 0;
-        {
-            const DevTask& tp = k->tp;
-            const int e = pl & 31;
-            float* R = sobs + (size_t)e * O;
-            loco_obs_root_pair(srec + e * g.P, tp, pl, R, spot, sprev, e < n && pw);
-        }
-        const LocoTerms lt = loco_reward_terms_pair(k->tp, D, sobs + (size_t)(pl & 31) * O,
-                                                    sobs + (size_t)(pl & 31) * O + ka, pl);
-        if (lane < n) {
-            const int i = e0 + lane;
-            const DevTask& tp = k->tp;
-            float* R = sobs + (size_t)lane * O;
-            const float p_new = spot[lane], p_old = sprev[lane];
-            rew[i] = loco_reward_total(tp, R[0], R[10], R[11], p_new, p_old, lt);
-            pot[i] = p_new;
-            prev[i] = p_old;
-            int64_t d = loco_done(tp, R[0], rb, progress);
-            if (nflag) {                                                // nan_guard
-                k->st.nan_flag[i] = 0;
-                atomicAdd(k->st.nan_total, 1ull);
-                d = 1;
-            }
-            reset_buf[i] = d;
-            progress_buf[i] = progress;
-        }
-        __syncthreads();
-        float* dst = obs + (size_t)e0 * O;
-        const int cnt = n * O;
-        if ((((uintptr_t)obs) & 15) == 0) {   // e0 * O * 4 B is a multiple of 128 B
-            const int n4 = cnt >> 2;
-            for (int kk = lane; kk < n4; kk += 64)
-                __builtin_nontemporal_store(reinterpret_cast<const v4f*>(sobs)[kk], reinterpret_cast<v4f*>(dst) + kk);
-            for (int kk = 4 * n4 + lane; kk < cnt; kk += 64) dst[kk] = sobs[kk];
-        } else {
-            for (int kk = lane; kk < cnt; kk += 64) dst[kk] = sobs[kk];
-        }
-        __syncthreads();                    // the next tile overwrites the LDS tiles
-    }
-#undef MI_PIPE_ISSUE
-}
-#endif
 
 // register budget of the wave kernels: TopoCT::kWaves waves per SIMD
 #define MI_WAVE_OCC __attribute__((amdgpu_waves_per_eu(T::kWaves, T::kWaves)))
@@ -1083,11 +944,75 @@ __global__ __launch_bounds__(512) MI_PAIR_OCC void k_env_step_pair(const KParams
     STAMP(14);
 }
 
-// launch a paired kernel for the topologies that have one (compiled, nv <= 32)
+// the topologies that have paired kernels (compiled, nv <= 32)
 template <class T>
 constexpr bool has_pair() {
     if constexpr (T::kCT) return T::nv <= 32;
     else return false;
+}
+
+// The step-kernel variant of a sim, chosen HERE and nowhere else: one lane per env, one env per
+// wave or two (s->wave, s->pair), the topology and the solver (with_topo), plain or with the
+// per-env parameter table (envp). f receives a tag with the variant's two kernels: `sim`
+// (World.step) and `env` (the fused env step). kWave: the kernel reads the KParams block (else
+// model, state and parameters by value, and the EnvP kernels the table as two more arguments);
+// kPair: its `sim` kernel also takes the state mirrors. The one-env-per-wave path has no EnvP
+// kernels (envp_ensure refuses the table there): f is not called for it and false is returned.
+struct ThreadStep {
+    static constexpr bool kWave = false, kPair = false, kEnvP = false;
+    static constexpr auto sim = &k_sim_step;
+    static constexpr auto env = &k_env_step;
+};
+struct ThreadStepEnvP {
+    static constexpr bool kWave = false, kPair = false, kEnvP = true;
+    static constexpr auto sim = &k_sim_step_envp;
+    static constexpr auto env = &k_env_step_envp;
+};
+template <class T>
+struct WaveStep {
+    static constexpr bool kWave = true, kPair = false, kEnvP = false;
+    static constexpr auto sim = &k_sim_step_wave<T>;
+    static constexpr auto env = &k_env_step_wave<T>;
+};
+template <class T>
+struct PairStep {
+    static constexpr bool kWave = true, kPair = true, kEnvP = T::kEnvP;
+    static constexpr auto sim = &k_sim_step_pair<T>;
+    static constexpr auto env = &k_env_step_pair<T>;
+};
+template <class F>
+static bool with_step_kernels(const mi_sim* s, bool envp, F&& f) {
+    bool found = false;
+    if (!s->wave) {
+        if (envp) f(ThreadStepEnvP{});
+        else f(ThreadStep{});
+        return true;
+    }
+    with_topo(s->topo, s->sp.tgs != 0, [&](auto T) {
+        using TT = decltype(T);
+        found = true;
+        if constexpr (has_pair<TT>()) {
+            if (s->pair) {
+                if (envp) f(PairStep<EnvP<TT>>{});
+                else f(PairStep<TT>{});
+                return;
+            }
+        }
+        if (envp) found = false;
+        else f(WaveStep<TT>{});
+    });
+    return found;
+}
+
+// the dynamic-LDS limit of a variant's two kernels (layouts above the default 64 KB)
+static int step_kernels_lds_limit(const mi_sim* s, bool envp) {
+    if (!s->wave || s->lds_bytes <= 64 * 1024) return MI_OK;
+    hipError_t e1 = hipSuccess, e2 = hipSuccess;
+    with_step_kernels(s, envp, [&](auto V) {
+        e1 = hipFuncSetAttribute((const void*)V.env, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes);
+        e2 = hipFuncSetAttribute((const void*)V.sim, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes);
+    });
+    return e1 == hipSuccess && e2 == hipSuccess ? MI_OK : MI_E_HIP;
 }
 
 // Randomizer.apply_{observations,actions}_randomization (randomize.py:212-260), modular path
@@ -1308,10 +1233,23 @@ int mi_debug_stamps_raw(unsigned long long* out, int slots) {
 #endif
 const char* mi_last_error(void) { return g_err.c_str(); }
 
-int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, int64_t off,
-                  int32_t device_id, const float* env_origins, uint64_t seed, mi_sim** out) {
-    if (!md || !prm || !out || !env_origins) return fail(MI_E_NULL, "mi_sim_create: null argument");
-    *out = nullptr;
+// ---- mi_sim_create, stage by stage (each returns the error code; mi_sim_create destroys the
+// half-built sim on the first failure) ------------------------------------------------------
+// what a stage hands on to later ones (host side only)
+struct CreateCtx {
+    const mi_model_desc* md;
+    const mi_sim_params* prm;
+    bool self_on = false;                                     // self-collision rows are built
+    std::vector<int> dof_parent, dof_link, pt_geom, pt_end;   // create_model
+    std::vector<int> chain_start, chain_list, desc_start, desc_list, anc_start;   // create_tree_tables
+    std::vector<unsigned long long> link_mask;
+};
+#define UP(field, src, cnt) if (int rc = upload(s, src, (size_t)(cnt), &m.field)) return rc
+#define UPW(field, vec) if (int rc = upload(s, vec.data(), vec.size(), &t.field)) return rc
+#define AL(field, T, cnt) if (int rc = dev_alloc(s, &p, sizeof(T) * (size_t)(cnt))) return rc; st.field = (T*)p
+
+// validation of the description (pure: nothing is allocated yet)
+static int create_validate(const mi_model_desc* md, int32_t N) {
     if (N <= 0) return fail(MI_E_SHAPE, "num_envs must be > 0 (got %d)", N);
     const int L = md->num_links;
     if (L < 1 || L - 1 > MI_MAXA) return fail(MI_E_MODEL, "num_links %d out of range [1,%d]", L, MI_MAXA + 1);
@@ -1339,20 +1277,13 @@ int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, 
     for (int q = 0; q < 2 * md->num_pairs; ++q)
         if (md->pairs[q] < 0 || md->pairs[q] >= md->num_geoms)
             return fail(MI_E_MODEL, "pairs[%d]=%d is not a geom index", q, md->pairs[q]);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_E_NODEV, "no HIP device visible");
-    if (device_id < 0 || device_id >= ndev) return fail(MI_E_NODEV, "device_id %d out of range (%d devices)", device_id, ndev);
-    HIP_TRY(hipSetDevice(device_id));
+    return MI_OK;
+}
 
-    mi_sim* s = new mi_sim();
-    s->device = device_id;
-    s->N = N;
-    if (const char* d = getenv("MI_SIM_DEFER")) s->defer = atoi(d) != 0;
-    if (const char* b = getenv("MI_SIM_BLOCK")) {
-        int v = atoi(b);
-        if (v >= 1 && v <= 1024) s->block = v;
-    }
-    auto cleanup = [&](int rc) { mi_sim_destroy(s); return rc; };
+// model derivation (DOF / contact-point tables, row budget, workspace slots) and upload
+static int create_model(mi_sim* s, CreateCtx& cx) {
+    const mi_model_desc* md = cx.md;
+    const int L = md->num_links;
     DevModel& m = s->dm;
     m.dyn = md->dyn_kind;
     m.root_free = md->root_free ? 1 : 0;
@@ -1362,9 +1293,11 @@ int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, 
     m.nv = m.nr + m.D;
     m.G = md->num_geoms;
     m.S = md->num_sensors;
-    if (m.nv > MI_MAXNV) return cleanup(fail(MI_E_MODEL, "too many dofs"));
+    if (m.nv > MI_MAXNV) return fail(MI_E_MODEL, "too many dofs");
     // derived tables
-    std::vector<int> dof_parent(m.nv > 0 ? m.nv : 1), dof_link(m.nv > 0 ? m.nv : 1), pt_geom, pt_end;
+    std::vector<int>&dof_parent = cx.dof_parent, &dof_link = cx.dof_link, &pt_geom = cx.pt_geom, &pt_end = cx.pt_end;
+    dof_parent.assign(m.nv > 0 ? m.nv : 1, 0);
+    dof_link.assign(m.nv > 0 ? m.nv : 1, 0);
     for (int k = 0; k < m.nr; ++k) { dof_parent[k] = k - 1; dof_link[k] = 0; }
     for (int l = 1; l < L; ++l) {
         const int k = m.nr + l - 1, P = md->parent[l];
@@ -1377,15 +1310,13 @@ int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, 
     }
     m.npts = (int)pt_geom.size();
     // self-collision rows share the MI_MAX_ROWS budget (mi_sim.h); ground + limit rows must fit
-    const bool self_on = prm->enable_self_collisions && md->num_pairs > 0 &&
+    const bool self_on = cx.self_on = cx.prm->enable_self_collisions && md->num_pairs > 0 &&
                          md->dyn_kind == MI_DYN_ARTICULATION;
     m.max_rows = 3 * m.npts + m.D;
     if (m.max_rows > MI_MAX_ROWS)
-        return cleanup(fail(MI_E_MODEL, "%d contact points + %d joints exceed the %d-row budget",
-                            m.npts, m.D, MI_MAX_ROWS));
+        return fail(MI_E_MODEL, "%d contact points + %d joints exceed the %d-row budget",
+                            m.npts, m.D, MI_MAX_ROWS);
     if (self_on) m.max_rows = std::min(MI_MAX_ROWS, 3 * (m.npts + md->num_pairs) + m.D);
-    int rc = 0;
-#define UP(field, src, cnt) if ((rc = upload(s, src, (size_t)(cnt), &m.field))) return cleanup(rc)
     UP(parent, md->parent, L); UP(jtype, md->jtype, L); UP(axis, md->axis, 3 * L);
     UP(pos, md->pos, 3 * L); UP(quat, md->quat, 4 * L); UP(mass, md->mass, L);
     UP(com, md->com, 3 * L); UP(inertia, md->inertia, 6 * L); UP(lower, md->lower, L);
@@ -1395,7 +1326,6 @@ int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, 
     UP(geom_p1, md->geom_p1, 3 * m.G); UP(geom_radius, md->geom_radius, m.G);
     UP(pt_geom, pt_geom.data(), pt_geom.size()); UP(pt_end, pt_end.data(), pt_end.size());
     UP(sensor_link, md->sensor_link, m.S); UP(sensor_pos, md->sensor_pos, 3 * m.S);
-#undef UP
     m.cart_mass = md->cart_mass; m.pole_mass = md->pole_mass; m.pole_com = md->pole_com;
     m.pole_inertia = md->pole_inertia; m.cart_damping = md->cart_damping;
     m.pole_damping = md->pole_damping;
@@ -1425,7 +1355,17 @@ int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, 
         m.o_cl = o; o += m.npts;
     }
     m.slots = o;
-    // wavefront-per-env path: eligibility + host-built tree tables + LDS layout
+    s->lower.assign(md->lower, md->lower + L);
+    s->upper.assign(md->upper, md->upper + L);
+    return MI_OK;
+}
+
+// kernel path (one lane or one wavefront per env) and compiled topology
+static int create_path(mi_sim* s, const CreateCtx& cx) {
+    const DevModel& m = s->dm;
+    const int L = m.L;
+    const bool self_on = cx.self_on;
+    // wavefront-per-env path: eligibility
     {
         const char* path = getenv("MI_SIM_PATH");
         const bool want_thread = path && std::string(path) == "thread";
@@ -1433,339 +1373,391 @@ int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, 
         s->wave = m.dyn == MI_DYN_ARTICULATION && !want_thread && m.nv <= WNV && m.npts <= 64 &&
                   m.max_rows <= 128 && L <= 64 && m.max_rows >= 6 * m.S + 3 * m.D;
         if (self_on && !s->wave)
-            return cleanup(fail(MI_E_MODEL, "self-collision needs the wavefront-per-env path "
-                                            "(one-lane-per-env path %s)", want_thread ? "forced by MI_SIM_PATH" : "selected"));
+            return fail(MI_E_MODEL, "self-collision needs the wavefront-per-env path "
+                                            "(one-lane-per-env path %s)", want_thread ? "forced by MI_SIM_PATH" : "selected");
     }
     if (s->wave) {
         const char* tsel = getenv("MI_SIM_TOPO");
-        s->topo = (tsel && std::string(tsel) == "runtime") ? 0 : match_topology(md, self_on);
-        WaveTabs& t = s->wt;
-        std::vector<int> depth(L, 0);
-        int maxd = 0;
-        for (int l = 1; l < L; ++l) { depth[l] = depth[md->parent[l]] + 1; maxd = std::max(maxd, depth[l]); }
-        t.nlev = maxd + 1;
-        std::vector<int> lev_start(t.nlev + 1, 0), lev_links;
-        for (int d = 0; d < t.nlev; ++d) {
-            lev_start[d] = (int)lev_links.size();
-            for (int l = 0; l < L; ++l) if (depth[l] == d) lev_links.push_back(l);
-        }
-        lev_start[t.nlev] = (int)lev_links.size();
-        std::vector<int> child_start(L + 1, 0), child_list;
-        for (int l = 0; l < L; ++l) {
-            child_start[l] = (int)child_list.size();
-            for (int c = l + 1; c < L; ++c) if (md->parent[c] == l) child_list.push_back(c);
-        }
-        child_start[L] = (int)child_list.size();
-        std::vector<int> desc_start(L + 1, 0), desc_list;
-        for (int l = 0; l < L; ++l) {
-            desc_start[l] = (int)desc_list.size();
-            for (int c = l + 1; c < L; ++c) {
-                int x = md->parent[c];
-                while (x > l) x = md->parent[x];
-                if (x == l) desc_list.push_back(c);
-            }
-        }
-        desc_start[L] = (int)desc_list.size();
-        if (desc_list.empty()) desc_list.push_back(0);
-        std::vector<int> anc_start(m.nv + 1, 0), anc_list;
-        int na_max = 0;
-        for (int k = 0; k < m.nv; ++k) {
-            anc_start[k] = (int)anc_list.size();
-            for (int j = dof_parent[k]; j >= 0; j = dof_parent[j]) anc_list.push_back(j);
-            na_max = std::max(na_max, (int)anc_list.size() - anc_start[k]);
-        }
-        anc_start[m.nv] = (int)anc_list.size();
-        std::vector<unsigned long long> link_mask(L, 0ull);
-        for (int l = 0; l < L; ++l) {
-            unsigned long long msk = 0ull;
-            for (int k = 0; k < m.nr; ++k) msk |= 1ull << k;
-            for (int x = l; x > 0; x = md->parent[x]) msk |= 1ull << (m.nr + x - 1);
-            link_mask[l] = msk;
-        }
-        std::vector<unsigned char> tri_p, tri_q;
-        for (int q = 0; q < na_max; ++q)
-            for (int p2 = 0; p2 <= q; ++p2) { tri_p.push_back((unsigned char)p2); tri_q.push_back((unsigned char)q); }
-        if (tri_p.empty()) { tri_p.push_back(0); tri_q.push_back(0); }
-        if (child_list.empty()) child_list.push_back(0);
-        if (anc_list.empty()) anc_list.push_back(0);
-#define UPW(field, vec) if ((rc = upload(s, vec.data(), vec.size(), &t.field))) return cleanup(rc)
-        UPW(lev_start, lev_start); UPW(lev_links, lev_links); UPW(child_start, child_start);
-        UPW(child_list, child_list); UPW(anc_start, anc_start); UPW(anc_list, anc_list);
-        UPW(desc_start, desc_start); UPW(desc_list, desc_list);
-        std::vector<int> chain_start(L + 1, 0), chain_list;
-        for (int l = 0; l < L; ++l) {
-            chain_start[l] = (int)chain_list.size();
-            std::vector<int> up;
-            for (int x = l; x > 0; x = md->parent[x]) up.push_back(x);
-            chain_list.insert(chain_list.end(), up.rbegin(), up.rend());
-        }
-        chain_start[L] = (int)chain_list.size();
-        if (chain_list.empty()) chain_list.push_back(0);
-        UPW(chain_start, chain_start); UPW(chain_list, chain_list);
-        UPW(link_mask, link_mask); UPW(tri_p, tri_p); UPW(tri_q, tri_q);
-        // per-model constant block (SoA), staged into LDS by every workgroup (McField & co.)
-        {
-            const int np = (int)pt_geom.size(), ns = md->num_sensors;
-            std::vector<float> mcb((size_t)MC_NLINKF * L, 0.0f);
-            for (int l = 0; l < L; ++l) {
-                auto put = [&](int f, float v) { mcb[(size_t)f * L + l] = v; };
-                for (int c = 0; c < 3; ++c) {
-                    put(MC_POS + c, md->pos[3 * l + c]); put(MC_AXIS + c, md->axis[3 * l + c]);
-                    put(MC_COM + c, md->com[3 * l + c]);
-                }
-                for (int c = 0; c < 4; ++c) put(MC_QUAT + c, md->quat[4 * l + c]);
-                for (int c = 0; c < 6; ++c) put(MC_INER + c, md->inertia[6 * l + c]);
-                put(MC_JTYPE, (float)md->jtype[l]); put(MC_MASS, md->mass[l]);
-                put(MC_ARM, md->armature[l]); put(MC_DAMP, md->damping[l]);
-                put(MC_LO, md->lower[l]); put(MC_HI, md->upper[l]);
-                const unsigned lo32 = (unsigned)(link_mask[l] & 0xffffffffull);
-                float mf; std::memcpy(&mf, &lo32, 4); put(MC_MASK, mf);
-            }
-            auto pad4 = [&]() { while (mcb.size() % 4) mcb.push_back(0.0f); };
-            pad4();
-            t.mc_pts = (int)mcb.size();
-            mcb.resize(mcb.size() + (size_t)MP_NF * np, 0.0f);
-            for (int c = 0; c < np; ++c) {
-                const int g = pt_geom[c];
-                const float* pg = pt_end[c] ? md->geom_p1 + 3 * g : md->geom_p0 + 3 * g;
-                mcb[t.mc_pts + (size_t)MP_LINK * np + c] = (float)md->geom_link[g];
-                for (int q = 0; q < 3; ++q) mcb[t.mc_pts + (size_t)(MP_X + q) * np + c] = pg[q];
-                mcb[t.mc_pts + (size_t)MP_RAD * np + c] = md->geom_radius[g];
-            }
-            pad4();
-            t.mc_sens = (int)mcb.size();
-            mcb.resize(mcb.size() + (size_t)MS_NF * ns, 0.0f);
-            for (int c = 0; c < ns; ++c) {
-                mcb[t.mc_sens + (size_t)MS_LINK * ns + c] = (float)md->sensor_link[c];
-                for (int q = 0; q < 3; ++q)
-                    mcb[t.mc_sens + (size_t)(MS_X + q) * ns + c] = md->sensor_pos[3 * c + q];
-            }
-            auto put_ints = [&](const std::vector<int>& v) {
-                pad4();
-                const int at = (int)mcb.size();
-                for (int x : v) { float f; std::memcpy(&f, &x, 4); mcb.push_back(f); }
-                return at;
-            };
-            t.mc_chs = put_ints(chain_start); t.mc_chl = put_ints(chain_list);
-            t.mc_dss = put_ints(desc_start); t.mc_dsl = put_ints(desc_list);
-            std::vector<int> lim;
-            for (int l = 1; l < L; ++l)
-                if (md->lower[l] < md->upper[l]) lim.push_back(l - 1);
-            t.nlimc = (int)lim.size();
-            if (lim.empty()) lim.push_back(0);
-            t.mc_lim = put_ints(lim);
-            // self-collision geometry: per geom (link, p0, p1, radius) and the geom pairs;
-            // global copies, and inside the LDS block when self-collision is on
-            std::vector<float> geo((size_t)8 * std::max(1, md->num_geoms), 0.0f);
-            for (int g = 0; g < md->num_geoms; ++g) {
-                geo[8 * g] = (float)md->geom_link[g];
-                for (int q = 0; q < 3; ++q) {
-                    geo[8 * g + 1 + q] = md->geom_p0[3 * g + q];
-                    geo[8 * g + 4 + q] = md->geom_p1[3 * g + q];
-                }
-                geo[8 * g + 7] = md->geom_radius[g];
-            }
-            std::vector<int> prs(md->pairs ? md->pairs : nullptr,
-                                 md->pairs ? md->pairs + 2 * md->num_pairs : nullptr);
-            if (prs.empty()) prs.assign(2, 0);
-            t.mc_geo = t.mc_pairs = -1;
-            if (self_on) {
-                pad4();
-                t.mc_geo = (int)mcb.size();
-                mcb.insert(mcb.end(), geo.begin(), geo.begin() + 8 * md->num_geoms);
-                // the pair table stays global (cache-resident, read once per substep by the
-                // broad phase): its LDS room goes to W rows
-            }
-            pad4();
-            t.mc_len = (int)mcb.size();
-            t.npts = np; t.nsens = ns;
-            UPW(g_mc, mcb);
-            UPW(g_geo, geo); UPW(g_pairs, prs);
-        }
-#undef UPW
-        auto al4 = [](int x) { return (x + 3) & ~3; };
-        const bool ct = s->topo != 0;
-        int so = 0;
-        auto take = [&](int n) { const int at = so; so += al4(n); return at; };
-        // Residency: the kernels' register budget allows TopoCT::kWaves waves per SIMD, i.e.
-        // envs_cu = 4 kWaves resident envs per CU (Humanoid 8, Ant 16: all 4096 envs of a launch
-        // in one round); the paired kernels hold 16 envs per CU (two per wave, 2 waves per SIMD).
-        // E envs per workgroup share one copy of the constant block; each env's region
-        // [s_R, s_total) gets the floats that leave envs_cu envs inside the CU's 160 KB.
-        int waves = 2, lam_rows = 0;
-        bool pair_ok = false;
-        with_topo(s->topo, s->sp.tgs != 0, [&](auto T) {
-            waves = decltype(T)::kWaves; lam_rows = decltype(T)::kLamRows;
-            pair_ok = has_pair<decltype(T)>();
-        });
-        // paired kernels (mi_pair.hpp, two envs per wavefront, 16 per workgroup, 2 waves per
-        // SIMD): the default for the compiled topologies (Humanoid 0.219 -> 0.205 ms, Ant 0.0765
-        // -> 0.0589 ms against their one-env-per-wave kernels at 2 and 4 waves per SIMD; 4096
-        // envs in one resident round either way); MI_WAVE_PAIR=0 selects one env per wave
-        const char* pe = getenv("MI_WAVE_PAIR");
-        const bool pair_want = pe ? atoi(pe) != 0 : true;
-        s->pair = ct && pair_ok && N % 2 == 0 && pair_want;
-        const int envs_cu = s->pair ? 16 : 4 * std::max(1, waves);
-        t.envs_per_wg = s->pair ? 16 : (ct && waves >= 4 ? 4 : 1);
-        if (const char* e = getenv("MI_WAVE_ENVS"); e && !s->pair) t.envs_per_wg = std::max(1, std::min(4, atoi(e)));
-        const int E = t.envs_per_wg;
-        const int env_budget = ((163840 / (int)sizeof(float)) / std::max(1, envs_cu / E) - al4(t.mc_len)) / E;
-        const int R = m.max_rows;
-        t.self_on = self_on ? 1 : 0;
-        t.npairs = self_on ? md->num_pairs : 0;
-        t.ncmax = std::min(m.npts + t.npairs, MI_MAX_ROWS / 3);
-        const int C = t.ncmax;
-        int lr = 0;   // CT path: published factor rows (each padded to 4) + 1/D (DofTree::lrow)
-        for (int k = 0; k < m.nv; ++k) lr += (anc_start[k + 1] - anc_start[k] + 3) & ~3;
-        bool overlay = false;
-        int span0 = 0, span1 = 0, ro = 0;
-        if (s->pair) {
-            // paired layout: the persistent regions first, then the P1-P4 span whose dead space
-            // takes the contact / row data and the W rows, which continue past the span up to
-            // the env's share (one W segment); no J rows (rebuilt), no second W segment
-            t.s_mc = take(t.mc_len);
-            t.s_R = take(9 * L); t.s_o = take(3 * L); t.s_S = take(6 * m.nv);
-            t.s_D = take(4); t.s_r = take(WNV); t.s_us = take(WNV); t.s_q = take(WNV); t.s_rp = take(8);
-            t.s_xs = take(4);
-            t.s_L = take(lr + m.nv);
-            t.j_rows_lds = 0;
-            t.s_J = take(4);
-            t.s_lam = take(4);
-            span0 = so;
-            t.s_F = take(16 * L); t.s_Ic = take(4); t.s_M = take(m.nv * m.nv); t.s_X = take(16 * L);
-            span1 = so;
-            overlay = true;
-            ro = span0;
-            auto take_r = [&](int n) { const int at = ro; ro += al4(n); return at; };
-            t.s_cp = take_r(3 * C); t.s_cl = take_r(C); t.s_cl2 = take_r(C); t.s_cn = take_r(3 * C);
-            // no row-kind array: the paired kernels derive a row's kind from its index (contact
-            // rows are (normal, friction, friction) triples, then the limit rows); its R floats
-            // buy W rows (Humanoid: 28 -> 32 LDS rows, so the narrow PGS never reads the slab)
-            t.s_rl = take_r(R); t.s_rb = take_r(R); t.s_rk = -1; t.s_ad = take_r(R);
-            t.s_lsg = take_r(WNV);
-            t.s_W = ro;
-            int w = std::min(64, (t.s_R + env_budget - ro) / m.nv);
-            while (w > 0 && ro + al4(w * m.nv) > t.s_R + env_budget) --w;
-            w &= ~3;   // whole 4-row groups (mi_pair.hpp pw_idx: DOF-major inside a group)
-            t.w_rows_lds = t.w_rows_a = std::max(0, w);
-            const char* spe = getenv("MI_SENS_PAR");
-            t.sens_par = (!spe || atoi(spe) != 0) && 6 * m.S * (C + 1) <= t.w_rows_lds * m.nv ? 1 : 0;
-            t.s_W2 = 0;
-            so = std::max(span1, ro + al4(t.w_rows_lds * m.nv));
-        } else {
-        t.s_mc = take(t.mc_len);
-        t.s_R = take(9 * L); t.s_o = take(3 * L); t.s_S = take(6 * m.nv);
-        // P1..P4 working span: link inertias / forces, M, aux (local transforms, composites).
-        // On the compiled-topology path it is dead once P4 has moved M into registers, and
-        // P8/P9 reuse it for the contact and row data and the first W rows.
-        span0 = so;
-        t.s_F = take(16 * L);   // per-link records: inertia (10) + Newton-Euler force (6)
-        t.s_Ic = take(4);       // (kept for the layout order; records live at s_F)
-        t.s_M = take(m.nv * m.nv);
-        t.s_X = take(16 * L);
-        span1 = so;
-        t.s_D = take(ct ? 4 : WNV); t.s_r = take(WNV); t.s_us = take(WNV);
-        t.s_q = take(WNV); t.s_rp = take(8);
-        // contacts: ground points + self pairs, at most MI_MAX_ROWS / 3 in total
-        const int rows_len = 8 * al4(C) + 4 * al4(R) + WNV;
-        overlay = ct && rows_len <= span1 - span0;
-        ro = overlay ? span0 : so;
-        auto take_r = [&](int n) { const int at = ro; ro += al4(n); return at; };
-        t.s_cp = take_r(3 * C); t.s_cl = take_r(C); t.s_cl2 = take_r(C); t.s_cn = take_r(3 * C);
-        t.s_rl = take_r(R);
-        t.s_rb = take_r(R); t.s_rk = take_r(R); t.s_ad = take_r(R); t.s_lsg = take_r(WNV);
-        if (!overlay) so = ro;
-        // lane-private solve vectors of the runtime-table solves (CT solves run in registers)
-        t.s_xs = take(ct ? 4 : WNV * 64);
-        t.s_L = take(ct ? lr + m.nv : 4);
-        // Residency: the kernels' register budget allows TopoCT::kWaves waves per SIMD, i.e.
-        // envs_cu = 4 kWaves resident envs per CU (Humanoid 8, Ant 16: all 4096 envs of a launch
-        // in one round). E envs per workgroup share one copy of the constant block; each env's
-        // region [s_R, s_total) gets the floats that leave envs_cu envs inside the CU's 160 KB.
-        // CT path: J rows of the first constraint rows for the PGS; a 16-envs/CU budget keeps
-        // the rows the Delassus-space sweeps use (kLamRows), the 8-envs/CU one up to 48; the
-        // paired kernels rebuild J rows instead
-        t.j_rows_lds = ct && !s->pair ? std::min(waves >= 4 ? lam_rows : 48, m.max_rows) : 0;
-        t.s_J = take(t.j_rows_lds > 0 ? t.j_rows_lds * m.nv : 4);
-        t.s_lam = take(4);
-        // CT path: W rows for the P9 -> P10 hand-over. First choice: the rest of the dead
-        // span; when that holds fewer rows than a one-bank PGS can use and the LDS budget of
-        // the wave path (8 envs / CU, 20 KB each) has room, a dedicated region instead, so
-        // the global slab is only the fallback of rare row-heavy substeps.
-        // Otherwise, a second segment at the end takes whatever rows the budget still holds
-        // (rows [w_rows_a, w_rows_lds) at s_W2).
-        t.s_W = ro;
-        t.w_rows_lds = overlay ? std::min(64, (span1 - ro) / m.nv) : 0;
-        t.w_rows_a = t.w_rows_lds;
-        t.s_W2 = 0;
-        {
-            const int want = std::min(64, m.max_rows);
-            const int lds_budget_floats = t.s_R + env_budget;   // end of this env's share
-            int fit = want;   // the most W rows a dedicated region can hold within the share
-            while (fit > 0 && so + al4(fit * m.nv) > lds_budget_floats) --fit;
-            if (ct && t.w_rows_lds < fit && (fit == want || !self_on || s->pair)) {
-                t.s_W = take(fit * m.nv);
-                t.w_rows_lds = t.w_rows_a = fit;
-            } else if (ct && self_on && t.w_rows_lds < want && !s->pair) {   // (w_row<kSelf> on device)
-                const int extra = std::min(want - t.w_rows_lds, (lds_budget_floats - so - 3) / m.nv);
-                if (extra > 0) {
-                    t.s_W2 = take(extra * m.nv);
-                    t.w_rows_lds += extra;
-                }
-            }
-        }
-        }
-        t.s_total = so;
-        // E envs per workgroup share the constant block [0, s_env); env w's region is shifted
-        // by w * env_stride
-        t.s_env = t.s_R;
-        t.env_stride = so - t.s_env;
-        if (!s->pair) {   // the sequential regions strictly increase; the row data sits inside the dead
-            // span (overlay) or between s_rp and s_xs
-            const int offs[] = {t.s_mc, t.s_R, t.s_o, t.s_S, t.s_F, t.s_Ic, t.s_M, t.s_X,
-                                t.s_D, t.s_r, t.s_us, t.s_q, t.s_rp, t.s_xs, t.s_L, t.s_J,
-                                t.s_lam, t.s_total};
-            for (size_t c = 1; c < sizeof(offs) / sizeof(offs[0]); ++c)
-                if (offs[c] <= offs[c - 1]) return cleanup(fail(MI_E_STATE, "wave LDS layout: region %zu overlaps", c));
-            const bool rows_ok = overlay ? (t.s_cp == span0 && ro <= span1)
-                                         : (t.s_cp > t.s_rp && ro <= t.s_xs);
-            if (!rows_ok) return cleanup(fail(MI_E_STATE, "wave LDS layout: row data misplaced"));
-        }
-        t.max_rows = m.max_rows;
-        t.g_row_stride = (size_t)m.max_rows * WNV;
-        // P8 self-collision scratch (segments + broad-phase survivors) in the same free span
-        t.ngeoms = md->num_geoms;
-        t.s_seg = -1; t.s_surv = -1;
-        if (overlay && self_on && al4(12 * md->num_geoms) + al4(md->num_pairs) <= span1 - ro) {
-            t.s_seg = ro;
-            t.s_surv = ro + al4(12 * md->num_geoms);
-        }
-        s->lds_bytes = (size_t)(so + (t.envs_per_wg - 1) * t.env_stride) * sizeof(float);
-        if (getenv("MI_SIM_DEBUG"))
-            fprintf(stderr, "[mi_sim] wave layout: pair=%d envs/wg=%d lds/wg=%zu B env_stride=%d floats "
-                            "mc=%d w_rows_lds=%d (a %d) j_rows_lds=%d s_seg=%d max_rows=%d ncmax=%d\n",
-                    (int)s->pair, t.envs_per_wg, s->lds_bytes, t.env_stride, t.mc_len, t.w_rows_lds,
-                    t.w_rows_a, t.j_rows_lds, t.s_seg, m.max_rows, t.ncmax);
-        if (s->pair && ((self_on && t.s_seg < 0) || s->lds_bytes > 163840))
-            return cleanup(fail(MI_E_STATE, "paired wave layout does not fit (%zu B of LDS per workgroup)",
-                                s->lds_bytes));
-        // the paired kernels' narrow PGS reads its W rows from LDS only (mi_pair.hpp WSrc)
-        if (s->pair && t.w_rows_lds < lam_rows)
-            return cleanup(fail(MI_E_STATE, "paired wave layout: %d LDS W rows < %d Delassus rows",
-                                t.w_rows_lds, lam_rows));
+        s->topo = (tsel && std::string(tsel) == "runtime") ? 0 : match_topology(cx.md, self_on);
     }
-    s->lower.assign(md->lower, md->lower + L);
-    s->upper.assign(md->upper, md->upper + L);
-    // params
+    return MI_OK;
+}
+
+// host-built tree tables of the wave kernels
+static int create_tree_tables(mi_sim* s, CreateCtx& cx) {
+    const mi_model_desc* md = cx.md;
+    const DevModel& m = s->dm;
+    WaveTabs& t = s->wt;
+    const int L = m.L;
+    const std::vector<int>& dof_parent = cx.dof_parent;
+    std::vector<int> depth(L, 0);
+    int maxd = 0;
+    for (int l = 1; l < L; ++l) { depth[l] = depth[md->parent[l]] + 1; maxd = std::max(maxd, depth[l]); }
+    t.nlev = maxd + 1;
+    std::vector<int> lev_start(t.nlev + 1, 0), lev_links;
+    for (int d = 0; d < t.nlev; ++d) {
+        lev_start[d] = (int)lev_links.size();
+        for (int l = 0; l < L; ++l) if (depth[l] == d) lev_links.push_back(l);
+    }
+    lev_start[t.nlev] = (int)lev_links.size();
+    std::vector<int> child_start(L + 1, 0), child_list;
+    for (int l = 0; l < L; ++l) {
+        child_start[l] = (int)child_list.size();
+        for (int c = l + 1; c < L; ++c) if (md->parent[c] == l) child_list.push_back(c);
+    }
+    child_start[L] = (int)child_list.size();
+    std::vector<int>&desc_start = cx.desc_start, &desc_list = cx.desc_list;
+    desc_start.assign(L + 1, 0);
+    for (int l = 0; l < L; ++l) {
+        desc_start[l] = (int)desc_list.size();
+        for (int c = l + 1; c < L; ++c) {
+            int x = md->parent[c];
+            while (x > l) x = md->parent[x];
+            if (x == l) desc_list.push_back(c);
+        }
+    }
+    desc_start[L] = (int)desc_list.size();
+    if (desc_list.empty()) desc_list.push_back(0);
+    std::vector<int>& anc_start = cx.anc_start;
+    anc_start.assign(m.nv + 1, 0);
+    std::vector<int> anc_list;
+    int na_max = 0;
+    for (int k = 0; k < m.nv; ++k) {
+        anc_start[k] = (int)anc_list.size();
+        for (int j = dof_parent[k]; j >= 0; j = dof_parent[j]) anc_list.push_back(j);
+        na_max = std::max(na_max, (int)anc_list.size() - anc_start[k]);
+    }
+    anc_start[m.nv] = (int)anc_list.size();
+    std::vector<unsigned long long>& link_mask = cx.link_mask;
+    link_mask.assign(L, 0ull);
+    for (int l = 0; l < L; ++l) {
+        unsigned long long msk = 0ull;
+        for (int k = 0; k < m.nr; ++k) msk |= 1ull << k;
+        for (int x = l; x > 0; x = md->parent[x]) msk |= 1ull << (m.nr + x - 1);
+        link_mask[l] = msk;
+    }
+    std::vector<unsigned char> tri_p, tri_q;
+    for (int q = 0; q < na_max; ++q)
+        for (int p2 = 0; p2 <= q; ++p2) { tri_p.push_back((unsigned char)p2); tri_q.push_back((unsigned char)q); }
+    if (tri_p.empty()) { tri_p.push_back(0); tri_q.push_back(0); }
+    if (child_list.empty()) child_list.push_back(0);
+    if (anc_list.empty()) anc_list.push_back(0);
+    UPW(lev_start, lev_start); UPW(lev_links, lev_links); UPW(child_start, child_start);
+    UPW(child_list, child_list); UPW(anc_start, anc_start); UPW(anc_list, anc_list);
+    UPW(desc_start, desc_start); UPW(desc_list, desc_list);
+    std::vector<int>&chain_start = cx.chain_start, &chain_list = cx.chain_list;
+    chain_start.assign(L + 1, 0);
+    for (int l = 0; l < L; ++l) {
+        chain_start[l] = (int)chain_list.size();
+        std::vector<int> up;
+        for (int x = l; x > 0; x = md->parent[x]) up.push_back(x);
+        chain_list.insert(chain_list.end(), up.rbegin(), up.rend());
+    }
+    chain_start[L] = (int)chain_list.size();
+    if (chain_list.empty()) chain_list.push_back(0);
+    UPW(chain_start, chain_start); UPW(chain_list, chain_list);
+    UPW(link_mask, link_mask); UPW(tri_p, tri_p); UPW(tri_q, tri_q);
+    return MI_OK;
+}
+
+static int create_constant_block(mi_sim* s, const CreateCtx& cx) {
+    const mi_model_desc* md = cx.md;
+    WaveTabs& t = s->wt;
+    const int L = s->dm.L;
+    const bool self_on = cx.self_on;
+    const std::vector<int>&pt_geom = cx.pt_geom, &pt_end = cx.pt_end, &chain_start = cx.chain_start,
+                          &chain_list = cx.chain_list, &desc_start = cx.desc_start, &desc_list = cx.desc_list;
+    const std::vector<unsigned long long>& link_mask = cx.link_mask;
+    // per-model constant block (SoA), staged into LDS by every workgroup (McField & co.)
+    {
+        const int np = (int)pt_geom.size(), ns = md->num_sensors;
+        std::vector<float> mcb((size_t)MC_NLINKF * L, 0.0f);
+        for (int l = 0; l < L; ++l) {
+            auto put = [&](int f, float v) { mcb[(size_t)f * L + l] = v; };
+            for (int c = 0; c < 3; ++c) {
+                put(MC_POS + c, md->pos[3 * l + c]); put(MC_AXIS + c, md->axis[3 * l + c]);
+                put(MC_COM + c, md->com[3 * l + c]);
+            }
+            for (int c = 0; c < 4; ++c) put(MC_QUAT + c, md->quat[4 * l + c]);
+            for (int c = 0; c < 6; ++c) put(MC_INER + c, md->inertia[6 * l + c]);
+            put(MC_JTYPE, (float)md->jtype[l]); put(MC_MASS, md->mass[l]);
+            put(MC_ARM, md->armature[l]); put(MC_DAMP, md->damping[l]);
+            put(MC_LO, md->lower[l]); put(MC_HI, md->upper[l]);
+            const unsigned lo32 = (unsigned)(link_mask[l] & 0xffffffffull);
+            float mf; std::memcpy(&mf, &lo32, 4); put(MC_MASK, mf);
+        }
+        auto pad4 = [&]() { while (mcb.size() % 4) mcb.push_back(0.0f); };
+        pad4();
+        t.mc_pts = (int)mcb.size();
+        mcb.resize(mcb.size() + (size_t)MP_NF * np, 0.0f);
+        for (int c = 0; c < np; ++c) {
+            const int g = pt_geom[c];
+            const float* pg = pt_end[c] ? md->geom_p1 + 3 * g : md->geom_p0 + 3 * g;
+            mcb[t.mc_pts + (size_t)MP_LINK * np + c] = (float)md->geom_link[g];
+            for (int q = 0; q < 3; ++q) mcb[t.mc_pts + (size_t)(MP_X + q) * np + c] = pg[q];
+            mcb[t.mc_pts + (size_t)MP_RAD * np + c] = md->geom_radius[g];
+        }
+        pad4();
+        t.mc_sens = (int)mcb.size();
+        mcb.resize(mcb.size() + (size_t)MS_NF * ns, 0.0f);
+        for (int c = 0; c < ns; ++c) {
+            mcb[t.mc_sens + (size_t)MS_LINK * ns + c] = (float)md->sensor_link[c];
+            for (int q = 0; q < 3; ++q)
+                mcb[t.mc_sens + (size_t)(MS_X + q) * ns + c] = md->sensor_pos[3 * c + q];
+        }
+        auto put_ints = [&](const std::vector<int>& v) {
+            pad4();
+            const int at = (int)mcb.size();
+            for (int x : v) { float f; std::memcpy(&f, &x, 4); mcb.push_back(f); }
+            return at;
+        };
+        t.mc_chs = put_ints(chain_start); t.mc_chl = put_ints(chain_list);
+        t.mc_dss = put_ints(desc_start); t.mc_dsl = put_ints(desc_list);
+        std::vector<int> lim;
+        for (int l = 1; l < L; ++l)
+            if (md->lower[l] < md->upper[l]) lim.push_back(l - 1);
+        t.nlimc = (int)lim.size();
+        if (lim.empty()) lim.push_back(0);
+        t.mc_lim = put_ints(lim);
+        // self-collision geometry: per geom (link, p0, p1, radius) and the geom pairs;
+        // global copies, and inside the LDS block when self-collision is on
+        std::vector<float> geo((size_t)8 * std::max(1, md->num_geoms), 0.0f);
+        for (int g = 0; g < md->num_geoms; ++g) {
+            geo[8 * g] = (float)md->geom_link[g];
+            for (int q = 0; q < 3; ++q) {
+                geo[8 * g + 1 + q] = md->geom_p0[3 * g + q];
+                geo[8 * g + 4 + q] = md->geom_p1[3 * g + q];
+            }
+            geo[8 * g + 7] = md->geom_radius[g];
+        }
+        std::vector<int> prs(md->pairs ? md->pairs : nullptr,
+                             md->pairs ? md->pairs + 2 * md->num_pairs : nullptr);
+        if (prs.empty()) prs.assign(2, 0);
+        t.mc_geo = t.mc_pairs = -1;
+        if (self_on) {
+            pad4();
+            t.mc_geo = (int)mcb.size();
+            mcb.insert(mcb.end(), geo.begin(), geo.begin() + 8 * md->num_geoms);
+            // the pair table stays global (cache-resident, read once per substep by the
+            // broad phase): its LDS room goes to W rows
+        }
+        pad4();
+        t.mc_len = (int)mcb.size();
+        t.npts = np; t.nsens = ns;
+        UPW(g_mc, mcb);
+        UPW(g_geo, geo); UPW(g_pairs, prs);
+    }
+    return MI_OK;
+}
+
+// The LDS layout of one env's region, as float offsets into WaveTabs: both layouts are filled from
+// the same inputs with the same cursor helpers.
+struct LdsLayout {
+    const DevModel& m;
+    WaveTabs& t;
+    bool ct, self_on;                            // compiled topology; self-collision rows
+    int L, lr, env_budget, R, C, waves, lam_rows;
+    int so = 0, ro = 0, span0 = 0, span1 = 0;    // cursors: sequential regions, row data; the P1-P4 span
+    bool overlay = false;                        // the row data sits inside the dead span
+    static int al4(int x) { return (x + 3) & ~3; }
+    int take(int n) { const int at = so; so += al4(n); return at; }
+    int take_r(int n) { const int at = ro; ro += al4(n); return at; }
+    void paired();
+    void one_per_wave();
+};
+
+void LdsLayout::paired() {
+    // paired layout: the persistent regions first, then the P1-P4 span whose dead space
+    // takes the contact / row data and the W rows, which continue past the span up to
+    // the env's share (one W segment); no J rows (rebuilt), no second W segment
+    t.s_mc = take(t.mc_len);
+    t.s_R = take(9 * L); t.s_o = take(3 * L); t.s_S = take(6 * m.nv);
+    t.s_D = take(4); t.s_r = take(WNV); t.s_us = take(WNV); t.s_q = take(WNV); t.s_rp = take(8);
+    t.s_xs = take(4);
+    t.s_L = take(lr + m.nv);
+    t.j_rows_lds = 0;
+    t.s_J = take(4);
+    t.s_lam = take(4);
+    span0 = so;
+    t.s_F = take(16 * L); t.s_Ic = take(4); t.s_M = take(m.nv * m.nv); t.s_X = take(16 * L);
+    span1 = so;
+    overlay = true;
+    ro = span0;
+    t.s_cp = take_r(3 * C); t.s_cl = take_r(C); t.s_cl2 = take_r(C); t.s_cn = take_r(3 * C);
+    // no row-kind array: the paired kernels derive a row's kind from its index (contact
+    // rows are (normal, friction, friction) triples, then the limit rows); its R floats
+    // buy W rows (Humanoid: 28 -> 32 LDS rows, so the narrow PGS never reads the slab)
+    t.s_rl = take_r(R); t.s_rb = take_r(R); t.s_rk = -1; t.s_ad = take_r(R);
+    t.s_lsg = take_r(WNV);
+    t.s_W = ro;
+    int w = std::min(64, (t.s_R + env_budget - ro) / m.nv);
+    while (w > 0 && ro + al4(w * m.nv) > t.s_R + env_budget) --w;
+    w &= ~3;   // whole 4-row groups (mi_pair.hpp pw_idx: DOF-major inside a group)
+    t.w_rows_lds = t.w_rows_a = std::max(0, w);
+    const char* spe = getenv("MI_SENS_PAR");
+    t.sens_par = (!spe || atoi(spe) != 0) && 6 * m.S * (C + 1) <= t.w_rows_lds * m.nv ? 1 : 0;
+    t.s_W2 = 0;
+    so = std::max(span1, ro + al4(t.w_rows_lds * m.nv));
+}
+
+void LdsLayout::one_per_wave() {
+    t.s_mc = take(t.mc_len);
+    t.s_R = take(9 * L); t.s_o = take(3 * L); t.s_S = take(6 * m.nv);
+    // P1..P4 working span: link inertias / forces, M, aux (local transforms, composites).
+    // On the compiled-topology path it is dead once P4 has moved M into registers, and
+    // P8/P9 reuse it for the contact and row data and the first W rows.
+    span0 = so;
+    t.s_F = take(16 * L);   // per-link records: inertia (10) + Newton-Euler force (6)
+    t.s_Ic = take(4);       // (kept for the layout order; records live at s_F)
+    t.s_M = take(m.nv * m.nv);
+    t.s_X = take(16 * L);
+    span1 = so;
+    t.s_D = take(ct ? 4 : WNV); t.s_r = take(WNV); t.s_us = take(WNV);
+    t.s_q = take(WNV); t.s_rp = take(8);
+    // contacts: ground points + self pairs, at most MI_MAX_ROWS / 3 in total
+    const int rows_len = 8 * al4(C) + 4 * al4(R) + WNV;
+    overlay = ct && rows_len <= span1 - span0;
+    ro = overlay ? span0 : so;
+    t.s_cp = take_r(3 * C); t.s_cl = take_r(C); t.s_cl2 = take_r(C); t.s_cn = take_r(3 * C);
+    t.s_rl = take_r(R);
+    t.s_rb = take_r(R); t.s_rk = take_r(R); t.s_ad = take_r(R); t.s_lsg = take_r(WNV);
+    if (!overlay) so = ro;
+    // lane-private solve vectors of the runtime-table solves (CT solves run in registers)
+    t.s_xs = take(ct ? 4 : WNV * 64);
+    t.s_L = take(ct ? lr + m.nv : 4);
+    // Residency: the kernels' register budget allows TopoCT::kWaves waves per SIMD, i.e.
+    // envs_cu = 4 kWaves resident envs per CU (Humanoid 8, Ant 16: all 4096 envs of a launch
+    // in one round). E envs per workgroup share one copy of the constant block; each env's
+    // region [s_R, s_total) gets the floats that leave envs_cu envs inside the CU's 160 KB.
+    // CT path: J rows of the first constraint rows for the PGS; a 16-envs/CU budget keeps
+    // the rows the Delassus-space sweeps use (kLamRows), the 8-envs/CU one up to 48; the
+    // paired kernels rebuild J rows instead
+    t.j_rows_lds = ct ? std::min(waves >= 4 ? lam_rows : 48, m.max_rows) : 0;
+    t.s_J = take(t.j_rows_lds > 0 ? t.j_rows_lds * m.nv : 4);
+    t.s_lam = take(4);
+    // CT path: W rows for the P9 -> P10 hand-over. First choice: the rest of the dead
+    // span; when that holds fewer rows than a one-bank PGS can use and the LDS budget of
+    // the wave path (8 envs / CU, 20 KB each) has room, a dedicated region instead, so
+    // the global slab is only the fallback of rare row-heavy substeps.
+    // Otherwise, a second segment at the end takes whatever rows the budget still holds
+    // (rows [w_rows_a, w_rows_lds) at s_W2).
+    t.s_W = ro;
+    t.w_rows_lds = overlay ? std::min(64, (span1 - ro) / m.nv) : 0;
+    t.w_rows_a = t.w_rows_lds;
+    t.s_W2 = 0;
+    {
+        const int want = std::min(64, m.max_rows);
+        const int lds_budget_floats = t.s_R + env_budget;   // end of this env's share
+        int fit = want;   // the most W rows a dedicated region can hold within the share
+        while (fit > 0 && so + al4(fit * m.nv) > lds_budget_floats) --fit;
+        if (ct && t.w_rows_lds < fit && (fit == want || !self_on)) {
+            t.s_W = take(fit * m.nv);
+            t.w_rows_lds = t.w_rows_a = fit;
+        } else if (ct && self_on && t.w_rows_lds < want) {   // (w_row<kSelf> on device)
+            const int extra = std::min(want - t.w_rows_lds, (lds_budget_floats - so - 3) / m.nv);
+            if (extra > 0) {
+                t.s_W2 = take(extra * m.nv);
+                t.w_rows_lds += extra;
+            }
+        }
+    }
+}
+
+static int create_lds_layout(mi_sim* s, const CreateCtx& cx) {
+    const mi_model_desc* md = cx.md;
+    const DevModel& m = s->dm;
+    WaveTabs& t = s->wt;
+    const int L = m.L, N = s->N;
+    const bool self_on = cx.self_on;
+    const std::vector<int>& anc_start = cx.anc_start;
+    auto al4 = [](int x) { return LdsLayout::al4(x); };
+    const bool ct = s->topo != 0;
+    // Residency: the kernels' register budget allows TopoCT::kWaves waves per SIMD, i.e.
+    // envs_cu = 4 kWaves resident envs per CU (Humanoid 8, Ant 16: all 4096 envs of a launch
+    // in one round); the paired kernels hold 16 envs per CU (two per wave, 2 waves per SIMD).
+    // E envs per workgroup share one copy of the constant block; each env's region
+    // [s_R, s_total) gets the floats that leave envs_cu envs inside the CU's 160 KB.
+    int waves = 2, lam_rows = 0;
+    bool pair_ok = false;
+    with_topo(s->topo, s->sp.tgs != 0, [&](auto T) {
+        waves = decltype(T)::kWaves; lam_rows = decltype(T)::kLamRows;
+        pair_ok = has_pair<decltype(T)>();
+    });
+    // paired kernels (mi_pair.hpp, two envs per wavefront, 16 per workgroup, 2 waves per
+    // SIMD): the default for the compiled topologies (Humanoid 0.219 -> 0.205 ms, Ant 0.0765
+    // -> 0.0589 ms against their one-env-per-wave kernels at 2 and 4 waves per SIMD; 4096
+    // envs in one resident round either way); MI_WAVE_PAIR=0 selects one env per wave
+    const char* pe = getenv("MI_WAVE_PAIR");
+    const bool pair_want = pe ? atoi(pe) != 0 : true;
+    s->pair = ct && pair_ok && N % 2 == 0 && pair_want;
+    const int envs_cu = s->pair ? 16 : 4 * std::max(1, waves);
+    t.envs_per_wg = s->pair ? 16 : (ct && waves >= 4 ? 4 : 1);
+    if (const char* e = getenv("MI_WAVE_ENVS"); e && !s->pair) t.envs_per_wg = std::max(1, std::min(4, atoi(e)));
+    const int E = t.envs_per_wg;
+    const int env_budget = ((163840 / (int)sizeof(float)) / std::max(1, envs_cu / E) - al4(t.mc_len)) / E;
+    const int R = m.max_rows;
+    t.self_on = self_on ? 1 : 0;
+    t.npairs = self_on ? md->num_pairs : 0;
+    t.ncmax = std::min(m.npts + t.npairs, MI_MAX_ROWS / 3);
+    const int C = t.ncmax;
+    int lr = 0;   // CT path: published factor rows (each padded to 4) + 1/D (DofTree::lrow)
+    for (int k = 0; k < m.nv; ++k) lr += (anc_start[k + 1] - anc_start[k] + 3) & ~3;
+    LdsLayout lay{m, t, ct, self_on, L, lr, env_budget, R, C, waves, lam_rows};
+    if (s->pair) lay.paired();
+    else lay.one_per_wave();
+    const int so = lay.so, ro = lay.ro, span0 = lay.span0, span1 = lay.span1;
+    const bool overlay = lay.overlay;
+    t.s_total = so;
+    // E envs per workgroup share the constant block [0, s_env); env w's region is shifted
+    // by w * env_stride
+    t.s_env = t.s_R;
+    t.env_stride = so - t.s_env;
+    if (!s->pair) {   // the sequential regions strictly increase; the row data sits inside the dead
+        // span (overlay) or between s_rp and s_xs
+        const int offs[] = {t.s_mc, t.s_R, t.s_o, t.s_S, t.s_F, t.s_Ic, t.s_M, t.s_X,
+                            t.s_D, t.s_r, t.s_us, t.s_q, t.s_rp, t.s_xs, t.s_L, t.s_J,
+                            t.s_lam, t.s_total};
+        for (size_t c = 1; c < sizeof(offs) / sizeof(offs[0]); ++c)
+            if (offs[c] <= offs[c - 1]) return fail(MI_E_STATE, "wave LDS layout: region %zu overlaps", c);
+        const bool rows_ok = overlay ? (t.s_cp == span0 && ro <= span1)
+                                     : (t.s_cp > t.s_rp && ro <= t.s_xs);
+        if (!rows_ok) return fail(MI_E_STATE, "wave LDS layout: row data misplaced");
+    }
+    t.max_rows = m.max_rows;
+    t.g_row_stride = (size_t)m.max_rows * WNV;
+    // P8 self-collision scratch (segments + broad-phase survivors) in the same free span
+    t.ngeoms = md->num_geoms;
+    t.s_seg = -1; t.s_surv = -1;
+    if (overlay && self_on && al4(12 * md->num_geoms) + al4(md->num_pairs) <= span1 - ro) {
+        t.s_seg = ro;
+        t.s_surv = ro + al4(12 * md->num_geoms);
+    }
+    s->lds_bytes = (size_t)(so + (t.envs_per_wg - 1) * t.env_stride) * sizeof(float);
+    if (getenv("MI_SIM_DEBUG"))
+        fprintf(stderr, "[mi_sim] wave layout: pair=%d envs/wg=%d lds/wg=%zu B env_stride=%d floats "
+                        "mc=%d w_rows_lds=%d (a %d) j_rows_lds=%d s_seg=%d max_rows=%d ncmax=%d\n",
+                (int)s->pair, t.envs_per_wg, s->lds_bytes, t.env_stride, t.mc_len, t.w_rows_lds,
+                t.w_rows_a, t.j_rows_lds, t.s_seg, m.max_rows, t.ncmax);
+    if (s->pair && ((self_on && t.s_seg < 0) || s->lds_bytes > 163840))
+        return fail(MI_E_STATE, "paired wave layout does not fit (%zu B of LDS per workgroup)",
+                            s->lds_bytes);
+    // the paired kernels' narrow PGS reads its W rows from LDS only (mi_pair.hpp WSrc)
+    if (s->pair && t.w_rows_lds < lam_rows)
+        return fail(MI_E_STATE, "paired wave layout: %d LDS W rows < %d Delassus rows",
+                            t.w_rows_lds, lam_rows);
+    return MI_OK;
+}
+
+static int create_params(mi_sim* s, const mi_sim_params* prm) {
     s->sp.dt = prm->dt;
     for (int k = 0; k < 3; ++k) s->sp.g[k] = prm->gravity[k];
     if (prm->solver_type != MI_SOLVER_PGS && prm->solver_type != MI_SOLVER_TGS)
-        return cleanup(fail(MI_E_ARG, "solver_type %d: this build implements 0 (PGS) and 1 (TGS)",
-                            prm->solver_type));
+        return fail(MI_E_ARG, "solver_type %d: this build implements 0 (PGS) and 1 (TGS)",
+                            prm->solver_type);
     if (prm->solver_iterations < 1 || prm->solver_iterations > 64 || prm->velocity_iterations < 0 ||
         prm->velocity_iterations > 64)
-        return cleanup(fail(MI_E_ARG, "solver iterations %d / velocity iterations %d out of range",
-                            prm->solver_iterations, prm->velocity_iterations));
+        return fail(MI_E_ARG, "solver iterations %d / velocity iterations %d out of range",
+                            prm->solver_iterations, prm->velocity_iterations);
     s->sp.iters = prm->solver_iterations;
     s->sp.tgs = prm->solver_type == MI_SOLVER_TGS ? 1 : 0;
     s->sp.viters = s->sp.tgs ? prm->velocity_iterations : 0;
@@ -1777,22 +1769,28 @@ int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, 
     s->sp.erp = prm->erp;
     s->sp.max_angvel = prm->max_angular_velocity;
     s->sp.ang_damp = prm->angular_damping;
-    if (!(prm->angular_damping >= 0.0f)) return cleanup(fail(MI_E_ARG, "angular_damping must be >= 0"));
-    // state
+    if (!(prm->angular_damping >= 0.0f)) return fail(MI_E_ARG, "angular_damping must be >= 0");
+    return MI_OK;
+}
+
+// state allocation and init
+static int create_state(mi_sim* s, int64_t off, uint64_t seed, const float* env_origins) {
+    const DevModel& m = s->dm;
+    const int N = s->N;
+    int rc = 0;
     DevState& st = s->ds;
     st.N = N;
     st.off = off;
     st.seed = seed;
     const int D = m.D > 0 ? m.D : 1, S = m.S > 0 ? m.S : 1;
     void* p = nullptr;
-#define AL(field, T, cnt) if ((rc = dev_alloc(s, &p, sizeof(T) * (size_t)(cnt)))) return cleanup(rc); st.field = (T*)p
     if (s->wave) {
         // one record per env: pos 3, quat 4, vel 6, q D, qd D, eff D, padded to whole 128-B
         // lines (the wave touches only its own lines, each access coalesced); the sensor
         // wrenches in a [N][6S] array of their own (DevState::sfs / ses)
         const int rec = (13 + 3 * D + 31) & ~31;
         float* r = nullptr;
-        if ((rc = dev_alloc(s, &p, sizeof(float) * (size_t)rec * N))) return cleanup(rc);
+        if ((rc = dev_alloc(s, &p, sizeof(float) * (size_t)rec * N))) return rc;
         r = (float*)p;
         st.fs = 1; st.es = rec;
         st.root_pos = r; st.root_quat = r + 3; st.root_vel = r + 7; st.q = r + 13;
@@ -1819,33 +1817,39 @@ int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, 
     }
     AL(nan_total, unsigned long long, 1);
     if (s->wave) {
-        if ((rc = dev_alloc(s, &p, sizeof(float) * (size_t)N * s->wt.g_row_stride))) return cleanup(rc);
+        if ((rc = dev_alloc(s, &p, sizeof(float) * (size_t)N * s->wt.g_row_stride))) return rc;
         s->rows = (float*)p;
         s->wt.g_wa = nullptr;
         if (s->pair) {   // wide-PGS scratch: kWideScratchRows x 64 lanes per wave (mi_pair.hpp)
             const size_t nb = sizeof(float) * (size_t)(N / 2) * 64 * (size_t)(kWideScratchRows > 0 ? kWideScratchRows : 1);
             size_t fr = 0, tot = 0;
             if (hipMemGetInfo(&fr, &tot) == hipSuccess && nb > fr)
-                return cleanup(fail(MI_E_ARG, "%d envs: the wide-PGS scratch needs %.1f MB (%d B per env), "
+                return fail(MI_E_ARG, "%d envs: the wide-PGS scratch needs %.1f MB (%d B per env), "
                                               "%.1f MB of device memory free", N, nb / 1e6,
-                                    (int)(nb / (size_t)N), fr / 1e6));
-            if ((rc = dev_alloc(s, &p, nb))) return cleanup(rc);
+                                    (int)(nb / (size_t)N), fr / 1e6);
+            if ((rc = dev_alloc(s, &p, nb))) return rc;
             s->wt.g_wa = (float*)p;
         }
         AL(ws, float, 64);
     } else {
         AL(ws, float, (size_t)((N + 63) / 64) * 64 * (m.slots > 0 ? m.slots : 1));
     }
-#undef AL
     std::vector<float> org((size_t)3 * N);
     for (int i = 0; i < N; ++i)
         for (int k = 0; k < 3; ++k) org[(size_t)k * N + i] = env_origins[(size_t)3 * i + k];
     const float* od = nullptr;
-    if ((rc = upload(s, org.data(), org.size(), &od))) return cleanup(rc);
+    if ((rc = upload(s, org.data(), org.size(), &od))) return rc;
     st.origins = od;
     hipLaunchKernelGGL(k_init_state, grid_for(s, N), dim3(s->block), 0, 0, st, m.D);
     hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) return cleanup(fail(MI_E_HIP, "init: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(MI_E_HIP, "init: %s", hipGetErrorString(e));
+    return MI_OK;
+}
+
+// nominal parameter record, KParams and the kernels' dynamic-LDS limit
+static int create_finish(mi_sim* s, const mi_model_desc* md) {
+    const DevModel& m = s->dm;
+    int rc = 0;
     {   // the sim-wide values in the order of a per-env parameter record (mi_get_env_params
         // before a table exists, the fill of a new table, the schedules' nominal operand)
         const int Dm = m.D;
@@ -1860,28 +1864,47 @@ int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, 
                 s->nominal[kEnvpDamping + Dm + j] = md->armature[j + 1];
             }
         }
-        if ((rc = upload(s, s->nominal.data(), s->nominal.size(), &s->nominal_dev))) return cleanup(rc);
+        if ((rc = upload(s, s->nominal.data(), s->nominal.size(), &s->nominal_dev))) return rc;
     }
-    if ((rc = sync_kparams(s))) return cleanup(rc);
-    if (s->wave && s->lds_bytes > 64 * 1024) {   // above the default dynamic-LDS limit
-        hipError_t e1 = hipSuccess, e2 = hipSuccess;
-        with_topo(s->topo, s->sp.tgs != 0, [&](auto T) {
-            if constexpr (has_pair<decltype(T)>()) {
-                if (s->pair) {
-                    e1 = hipFuncSetAttribute((const void*)k_env_step_pair<decltype(T)>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes);
-                    e2 = hipFuncSetAttribute((const void*)k_sim_step_pair<decltype(T)>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes);
-                    return;
-                }
-            }
-            e1 = hipFuncSetAttribute((const void*)k_env_step_wave<decltype(T)>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes);
-            e2 = hipFuncSetAttribute((const void*)k_sim_step_wave<decltype(T)>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes);
-        });
-        if (e1 != hipSuccess || e2 != hipSuccess)
-            return cleanup(fail(MI_E_HIP, "wave kernels: %zu B of LDS per workgroup refused", s->lds_bytes));
+    if ((rc = sync_kparams(s))) return rc;
+    if (step_kernels_lds_limit(s, false))   // the EnvP kernels get theirs with the table (envp_ensure)
+        return fail(MI_E_HIP, "wave kernels: %zu B of LDS per workgroup refused", s->lds_bytes);
+    return MI_OK;
+}
+#undef UP
+#undef UPW
+#undef AL
+
+int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, int64_t off,
+                  int32_t device_id, const float* env_origins, uint64_t seed, mi_sim** out) {
+    if (!md || !prm || !out || !env_origins) return fail(MI_E_NULL, "mi_sim_create: null argument");
+    *out = nullptr;
+    if (int rc = create_validate(md, N)) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_E_NODEV, "no HIP device visible");
+    if (device_id < 0 || device_id >= ndev) return fail(MI_E_NODEV, "device_id %d out of range (%d devices)", device_id, ndev);
+    HIP_TRY(hipSetDevice(device_id));
+
+    mi_sim* s = new mi_sim();
+    s->device = device_id;
+    s->N = N;
+    if (const char* d = getenv("MI_SIM_DEFER")) s->defer = atoi(d) != 0;
+    if (const char* b = getenv("MI_SIM_BLOCK")) {
+        int v = atoi(b);
+        if (v >= 1 && v <= 1024) s->block = v;
+    }
+    CreateCtx cx{md, prm};
+    int rc = create_model(s, cx);
+    if (!rc) rc = create_path(s, cx);
+    if (!rc && s->wave) rc = create_tree_tables(s, cx);
+    if (!rc && s->wave) rc = create_constant_block(s, cx);
+    if (!rc && s->wave) rc = create_lds_layout(s, cx);
+    if (!rc) rc = create_params(s, prm);   // (after the layout, which reads the solver-independent topology constants)
+    if (!rc) rc = create_state(s, off, seed, env_origins);
+    if (!rc) rc = create_finish(s, md);
+    if (rc) {
+        mi_sim_destroy(s);
+        return rc;
     }
     *out = s;
     return MI_OK;
@@ -1964,31 +1987,23 @@ static int launch_sim(mi_sim* s, int substeps, hipStream_t stream) {
     const bool mirrored = s->wave && s->pair && s->mir[0] && s->dm.nr == 6 && (s->dm.S == 0 || s->mir[5]);
     if (mirrored)
         if (int rc = order_mirror_write(s, stream)) return rc;
-    if (s->wave)
-        with_topo(s->topo, s->sp.tgs != 0, [&](auto T) {
-            if constexpr (has_pair<decltype(T)>()) {
-                if (s->pair) {
-                    Mirrors mir{};
-                    if (mirrored)
-                        for (int k = 0; k < 6; ++k) mir.p[k] = s->mir[k];
-                    if (s->envp)
-                        hipLaunchKernelGGL(k_sim_step_pair<EnvP<decltype(T)>>, wave_grid(s), wave_block(s),
-                                           s->lds_bytes, stream, (const KParams*)s->kp_dev, substeps, mir);
-                    else
-                        hipLaunchKernelGGL(k_sim_step_pair<decltype(T)>, wave_grid(s), wave_block(s), s->lds_bytes,
-                                           stream, (const KParams*)s->kp_dev, substeps, mir);
-                    return;
-                }
-            }
-            hipLaunchKernelGGL(k_sim_step_wave<decltype(T)>, wave_grid(s), wave_block(s), s->lds_bytes,
-                               stream, (const KParams*)s->kp_dev, substeps);
-        });
-    else if (s->envp)
-        hipLaunchKernelGGL(k_sim_step_envp, grid_for(s, s->N), dim3(s->block), 0, stream, s->dm, s->ds,
-                           s->sp, substeps, (const float*)s->envp, s->envp_stride);
-    else
-        hipLaunchKernelGGL(k_sim_step, grid_for(s, s->N), dim3(s->block), 0, stream, s->dm, s->ds,
-                           s->sp, substeps);
+    with_step_kernels(s, s->envp != nullptr, [&](auto V) {
+        const KParams* kp = (const KParams*)s->kp_dev;
+        if constexpr (decltype(V)::kPair) {
+            Mirrors mir{};
+            if (mirrored)
+                for (int k = 0; k < 6; ++k) mir.p[k] = s->mir[k];
+            launch(V.sim, wave_grid(s), wave_block(s), s->lds_bytes, stream, nullptr, nullptr, kp, substeps, mir);
+        } else if constexpr (decltype(V)::kWave) {
+            launch(V.sim, wave_grid(s), wave_block(s), s->lds_bytes, stream, nullptr, nullptr, kp, substeps);
+        } else if constexpr (decltype(V)::kEnvP) {
+            launch(V.sim, grid_for(s, s->N), dim3(s->block), 0, stream, nullptr, nullptr, s->dm, s->ds, s->sp,
+                   substeps, s->envp, s->envp_stride);
+        } else {
+            launch(V.sim, grid_for(s, s->N), dim3(s->block), 0, stream, nullptr, nullptr, s->dm, s->ds, s->sp,
+                   substeps);
+        }
+    });
     LAUNCH_CHECK();
     if (mirrored) return publish_mirrors(s, stream);   // valid after this launch (mi_get_state_mirror)
     return MI_OK;
@@ -2374,20 +2389,18 @@ int mi_task_post_step(mi_sim* s, const float* actions, float* obs, float* rew, i
             // kernel. Crossover: MI_POST_PIPE_MIN tiles per workgroup (default 2).
             const char* pm = getenv("MI_POST_PIPE_MIN");   // tiles per workgroup (tuning)
             if (!g && ntiles < (pm ? atoi(pm) : 2) * grid) goto one_tile;
-            const KParams* kp = (const KParams*)s->kp_dev;
             hipEvent_t ev0 = nullptr, ev1 = nullptr;
             HIP_TRY(timed_launch(s, stream, &ev0, &ev1));
-#define POST_PIPE(T, R, Q, W) do { if (ev0) hipExtLaunchKernelGGL((k_loco_post_pipe<T, R, Q, W>), dim3(grid), dim3(64), (uint32_t)tile, \
-            STREAM(stream), ev0, ev1, 0, kp, actions, obs, rew, reset_buf, progress_buf, potentials, prev_potentials); \
-            else hipLaunchKernelGGL((k_loco_post_pipe<T, R, Q, W>), dim3(grid), dim3(64), tile, STREAM(stream), kp, \
-            actions, obs, rew, reset_buf, progress_buf, potentials, prev_potentials); } while (0)
+            auto go = [&](auto kernel) {
+                launch(kernel, dim3(grid), dim3(64), tile, STREAM(stream), ev0, ev1, (const KParams*)s->kp_dev,
+                       actions, obs, rew, reset_buf, progress_buf, potentials, prev_potentials);
+            };
             switch (combo) {
-                case 1: POST_PIPE(32, 7, 2, 11); break;
-                case 2: POST_PIPE(32, 4, 3, 8); break;
-                case 3: POST_PIPE(16, 4, 1, 6); break;
-                default: POST_PIPE(16, 2, 2, 4); break;
+                case 1: go(k_loco_post_pipe<32, 7, 2, 11>); break;
+                case 2: go(k_loco_post_pipe<32, 4, 3, 8>); break;
+                case 3: go(k_loco_post_pipe<16, 4, 1, 6>); break;
+                default: go(k_loco_post_pipe<16, 2, 2, 4>); break;
             }
-#undef POST_PIPE
             LAUNCH_CHECK();
             s->post_kernel = var; s->post_grid = grid;
             return MI_OK;
@@ -2395,25 +2408,13 @@ int mi_task_post_step(mi_sim* s, const float* actions, float* obs, float* rew, i
     one_tile:
         var = 2;      // shapes / sizes the pipelined kernel does not take: the one-tile kernel
     }
-    const int te = var < 2 ? 64 : 32;
-    const bool stage = (var & 1) == 0;
-    const size_t tile = post_tile_lds(te, stage, s->ds.es, s->tp.A, s->tp.O, s->dm.D, s->dm.S);
+    const size_t tile = post_tile_lds(s->tp.O, s->dm.D, s->dm.S);
     if (s->tp.kind != MI_TASK_CARTPOLE && s->ds.fs == 1 && tile <= 64 * 1024) {
-        const dim3 g((s->N + te - 1) / te);
+        const dim3 g((s->N + kPostTileEnvs - 1) / kPostTileEnvs);
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         HIP_TRY(timed_launch(s, stream, &ev0, &ev1));
-#define POST_TILED(TE, ST) do { if (ev0) hipExtLaunchKernelGGL((k_loco_post_tiled<TE, ST>), g, dim3(64), (uint32_t)tile, \
-            STREAM(stream), ev0, ev1, 0, s->dm, s->ds, s->tp, actions, obs, rew, reset_buf, progress_buf, potentials, \
-            prev_potentials); \
-            else hipLaunchKernelGGL((k_loco_post_tiled<TE, ST>), g, dim3(64), tile, STREAM(stream), \
-            s->dm, s->ds, s->tp, actions, obs, rew, reset_buf, progress_buf, potentials, prev_potentials); } while (0)
-        switch (var) {
-            case 0: POST_TILED(64, true); break;
-            case 1: POST_TILED(64, false); break;
-            case 2: POST_TILED(32, true); break;
-            default: POST_TILED(32, false); break;
-        }
-#undef POST_TILED
+        launch(k_loco_post_tiled, g, dim3(64), tile, STREAM(stream), ev0, ev1, s->dm, s->ds, s->tp, actions, obs,
+               rew, reset_buf, progress_buf, potentials, prev_potentials);
         s->post_kernel = var; s->post_grid = (int)g.x;
     } else {
         hipLaunchKernelGGL(k_post_step, grid_for(s, s->N), dim3(s->block), 0, STREAM(stream), s->dm,
@@ -2502,70 +2503,21 @@ int mi_env_step(mi_sim* s, const float* actions, int32_t substeps, float* obs_ou
         if (int rc = dr_phys_step(s, reset_buf, STREAM(stream))) return rc;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     HIP_TRY(timed_launch(s, stream, &ev0, &ev1));
-    if (s->wave && s->tp.kind != MI_TASK_CARTPOLE)
-        with_topo(s->topo, s->sp.tgs != 0, [&](auto T) {
-            if constexpr (has_pair<decltype(T)>()) {
-                if (s->pair && s->envp) {
-                    using TE = EnvP<decltype(T)>;
-                    if (ev0)
-                        hipExtLaunchKernelGGL(k_env_step_pair<TE>, wave_grid(s), wave_block(s),
-                                              (uint32_t)s->lds_bytes, STREAM(stream), ev0, ev1, 0,
-                                              (const KParams*)s->kp_dev, actions, substeps, obs_out, obs_task,
-                                              rew, reset_buf, progress_buf, potentials, prev_potentials,
-                                              actions_out, rew_out, reset_out);
-                    else
-                        hipLaunchKernelGGL(k_env_step_pair<TE>, wave_grid(s), wave_block(s), s->lds_bytes,
-                                           STREAM(stream), (const KParams*)s->kp_dev, actions, substeps,
-                                           obs_out, obs_task, rew, reset_buf, progress_buf, potentials,
-                                           prev_potentials, actions_out, rew_out, reset_out);
-                    return;
-                }
-                if (s->pair) {
-                    if (ev0)
-                        hipExtLaunchKernelGGL(k_env_step_pair<decltype(T)>, wave_grid(s), wave_block(s),
-                                              (uint32_t)s->lds_bytes, STREAM(stream), ev0, ev1, 0,
-                                              (const KParams*)s->kp_dev, actions, substeps, obs_out, obs_task,
-                                              rew, reset_buf, progress_buf, potentials, prev_potentials,
-                                              actions_out, rew_out, reset_out);
-                    else
-                        hipLaunchKernelGGL(k_env_step_pair<decltype(T)>, wave_grid(s), wave_block(s), s->lds_bytes,
-                                           STREAM(stream), (const KParams*)s->kp_dev, actions, substeps,
-                                           obs_out, obs_task, rew, reset_buf, progress_buf, potentials,
-                                           prev_potentials, actions_out, rew_out, reset_out);
-                    return;
-                }
-            }
-            if (ev0)
-                hipExtLaunchKernelGGL(k_env_step_wave<decltype(T)>, wave_grid(s), wave_block(s),
-                                      (uint32_t)s->lds_bytes, STREAM(stream), ev0, ev1, 0,
-                                      (const KParams*)s->kp_dev, actions, substeps, obs_out, obs_task,
-                                      rew, reset_buf, progress_buf, potentials, prev_potentials,
-                                      actions_out, rew_out, reset_out);
-            else
-                hipLaunchKernelGGL(k_env_step_wave<decltype(T)>, wave_grid(s), wave_block(s), s->lds_bytes,
-                                   STREAM(stream), (const KParams*)s->kp_dev, actions, substeps,
-                                   obs_out, obs_task, rew, reset_buf, progress_buf, potentials,
-                                   prev_potentials, actions_out, rew_out, reset_out);
-        });
-    else if (s->envp && ev0)
-        hipExtLaunchKernelGGL(k_env_step_envp, grid_for(s, s->N), dim3(s->block), 0u, STREAM(stream), ev0, ev1, 0,
-                              s->dm, s->ds, s->sp, s->tp, actions, substeps, obs_out, obs_task, rew,
-                              reset_buf, progress_buf, potentials, prev_potentials, actions_out, rew_out,
-                              reset_out, (const float*)s->envp, s->envp_stride);
-    else if (s->envp)
-        hipLaunchKernelGGL(k_env_step_envp, grid_for(s, s->N), dim3(s->block), 0, STREAM(stream), s->dm,
-                           s->ds, s->sp, s->tp, actions, substeps, obs_out, obs_task, rew, reset_buf,
-                           progress_buf, potentials, prev_potentials, actions_out, rew_out, reset_out,
-                           (const float*)s->envp, s->envp_stride);
-    else if (ev0)
-        hipExtLaunchKernelGGL(k_env_step, grid_for(s, s->N), dim3(s->block), 0u, STREAM(stream), ev0, ev1, 0,
-                              s->dm, s->ds, s->sp, s->tp, actions, substeps, obs_out, obs_task, rew,
-                              reset_buf, progress_buf, potentials, prev_potentials, actions_out, rew_out,
-                              reset_out);
-    else
-        hipLaunchKernelGGL(k_env_step, grid_for(s, s->N), dim3(s->block), 0, STREAM(stream), s->dm,
-                           s->ds, s->sp, s->tp, actions, substeps, obs_out, obs_task, rew, reset_buf,
-                           progress_buf, potentials, prev_potentials, actions_out, rew_out, reset_out);
+    // (a wave-path sim never runs the cart-pole task: mi_task_configure ties it to cart-pole dynamics)
+    with_step_kernels(s, s->envp != nullptr, [&](auto V) {
+        if constexpr (decltype(V)::kWave)
+            launch(V.env, wave_grid(s), wave_block(s), s->lds_bytes, STREAM(stream), ev0, ev1,
+                   (const KParams*)s->kp_dev, actions, substeps, obs_out, obs_task, rew, reset_buf, progress_buf,
+                   potentials, prev_potentials, actions_out, rew_out, reset_out);
+        else if constexpr (decltype(V)::kEnvP)
+            launch(V.env, grid_for(s, s->N), dim3(s->block), 0, STREAM(stream), ev0, ev1, s->dm, s->ds, s->sp,
+                   s->tp, actions, substeps, obs_out, obs_task, rew, reset_buf, progress_buf, potentials,
+                   prev_potentials, actions_out, rew_out, reset_out, s->envp, s->envp_stride);
+        else
+            launch(V.env, grid_for(s, s->N), dim3(s->block), 0, STREAM(stream), ev0, ev1, s->dm, s->ds, s->sp,
+                   s->tp, actions, substeps, obs_out, obs_task, rew, reset_buf, progress_buf, potentials,
+                   prev_potentials, actions_out, rew_out, reset_out);
+    });
     LAUNCH_CHECK();
     return MI_OK;
 }
@@ -2692,20 +2644,9 @@ static int envp_ensure(mi_sim* s, hipStream_t stream, const char* fn) {
                        (float*)p, stride, recw, s->nominal_dev, s->N);
     LAUNCH_CHECK();
     HIP_TRY(hipStreamSynchronize(stream));   // first use only: later calls on any stream see the fill
-    if (s->wave && s->lds_bytes > 64 * 1024) {   // the EnvP instantiations' dynamic-LDS limit
-        hipError_t e1 = hipSuccess, e2 = hipSuccess;
-        with_topo(s->topo, s->sp.tgs != 0, [&](auto T) {
-            if constexpr (has_pair<decltype(T)>()) {
-                e1 = hipFuncSetAttribute((const void*)k_env_step_pair<EnvP<decltype(T)>>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes);
-                e2 = hipFuncSetAttribute((const void*)k_sim_step_pair<EnvP<decltype(T)>>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes);
-            }
-        });
-        if (e1 != hipSuccess || e2 != hipSuccess) {
-            free_tracked(s, p);
-            return fail(MI_E_HIP, "%s: %zu B of LDS per workgroup refused", fn, s->lds_bytes);
-        }
+    if (step_kernels_lds_limit(s, true)) {   // the EnvP instantiations' dynamic-LDS limit
+        free_tracked(s, p);
+        return fail(MI_E_HIP, "%s: %zu B of LDS per workgroup refused", fn, s->lds_bytes);
     }
     s->envp = (float*)p;
     s->envp_stride = stride;

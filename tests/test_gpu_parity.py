@@ -353,7 +353,8 @@ def test_pipelined_post_step_equals_one_tile(gpu, monkeypatch, name):
     start = {b: getattr(t, b).clone() for b in bufs}
     h, s = t.get_robot().handle, t.get_robot().stream()
     out = {}
-    for var, grid in (("32s", None), ("32p", "7"), ("32p", None), ("16p", "7")):
+    # 64s: a retired value of MI_POST_TILE, which selects the default kernel as an unset one does
+    for var, grid in (("32s", None), ("32p", "7"), ("32p", None), ("16p", "7"), ("64s", "7")):
         for b in bufs:
             getattr(t, b).copy_(start[b])
         monkeypatch.setenv("MI_POST_TILE", var)
@@ -369,13 +370,14 @@ def test_pipelined_post_step_equals_one_tile(gpu, monkeypatch, name):
         out[(var, grid)] = {b: getattr(t, b).clone() for b in bufs}
         kname, kgrid = t.get_robot().post_kernel()
         # 129 tiles without MI_POST_GRID: under two tiles per resident workgroup, the one-tile kernel
-        want = {"32p": "k_loco_post_pipe", "16p": "k_loco_post_pipe<16>"}.get(var) if grid else "k_loco_post_tiled<32s>"
+        want = ({"32p": "k_loco_post_pipe", "16p": "k_loco_post_pipe<16>", "64s": "k_loco_post_pipe"}.get(var)
+                if grid else "k_loco_post_tiled<32s>")
         assert kname == want, (var, grid, kname)
         if grid:
             assert kgrid == int(grid)
     ref = out[("32s", None)]
     assert not torch.equal(ref["obs_buf"], start["obs_buf"])
-    for key in (("32p", "7"), ("32p", None), ("16p", "7")):
+    for key in (("32p", "7"), ("32p", None), ("16p", "7"), ("64s", "7")):
         for b in bufs:
             assert torch.equal(out[key][b], ref[b]), (key, b)
     env.close()
