@@ -5,7 +5,10 @@
 // one env, so every instruction advances two envs, and a workgroup of 8 waves holds 16 envs —
 // the whole per-CU share of a 4096-env launch resident in ONE round (the wave kernel runs two
 // rounds of 8 envs per CU: its registers allow 2 waves per SIMD). Same algorithm, same constraint
-// rows in the same order, same task math as mi_wave.hpp and the oracle; what changes is the
+// rows in the same order, same task math as mi_wave.hpp and the oracle. P3 and the pre-physics
+// task layer are the very functions the wave kernel runs (mi_phase.hpp, G = Grp32); the other
+// phases are written out here for the 32-lane mapping, and a change to one of them has to be
+// made in mi_wave.hpp as well (DESIGN.md section 2 says which and why). What changes is the
 // mapping:
 //   * lane = lane & 31 inside the env's half; cross-lane broadcasts read the half's own lane
 //     (pbc: two v_readlane + a select), ballots are taken per half (hballot);
@@ -39,7 +42,6 @@
 
 namespace mi {
 
-MI_D int pair_l64() { return (int)(threadIdx.x & 63u); }
 // v of lane k of this lane's half (k wave-uniform)
 MI_D float pbc(float v, int k) {
     const float a = readlane(v, k), b = readlane(v, k + 32);
@@ -110,31 +112,6 @@ MI_D float ct_ltdl_pair(int lane, float (&Mc)[T::nvc]) {
     return dvec;
 }
 
-// Per-DOF loop over the motion subspaces S_c (6 floats per DOF in LDS, uniform per half) and,
-// with R, the rhs entries R[c]: fn(c, S_c, R[c]) with the loads of DOF c + SP issued before DOF c's
-// arithmetic, into a ring of SP + 1 buffers indexed at compile time. Each DOF's arithmetic is a
-// handful of VALU ops, so with the loads in line every DOF exposed a full LDS round trip.
-// S0: the first DOF whose S_c is read (the callers that know S_c of the free root's six DOFs
-// at compile time pass TP::nr; fn then gets an unread sv for c < S0).
-template <class TP, int SP, bool WITH_R, int S0 = 0, class F>
-MI_D void sdof_loop(const float* Ss, const float* R, F&& fn) {
-    constexpr int NB = SP + 1;
-    float sb[NB][6], rb[NB];
-    auto load = [&](auto C) {
-        constexpr int c = C;
-        if constexpr (c >= S0) {
-#pragma unroll
-            for (int q = 0; q < 6; ++q) sb[c % NB][q] = Ss[6 * c + q];
-        }
-        if constexpr (WITH_R) rb[c % NB] = R[c];
-    };
-    sfor<0, (SP < TP::nv ? SP : TP::nv)>([&](auto C) { load(C); });
-    sfor<0, TP::nv>([&](auto C) {
-        constexpr int c = C;
-        if constexpr (c + SP < TP::nv) load(std::integral_constant<int, c + SP>{});
-        fn(C, sb[c % NB], WITH_R ? rb[c % NB] : 0.0f);
-    });
-}
 #ifndef MI_PAIR_WIDE_PD
 #define MI_PAIR_WIDE_PD 16   // W-row prefetch depth of the wide Delassus set-up (A/B round 4: 4 0.1360, 8 0.1335, 12 0.1331 ms; later 12 0.1240, 16 0.1226)
 #endif
@@ -160,13 +137,6 @@ constexpr int kWideScratchRows = 64 - MI_PAIR_WIDE_AREG;
 #ifndef MI_PAIR_JREUSE_MAXNV
 #define MI_PAIR_JREUSE_MAXNV 16   // narrow PGS reuses P9's J rows for models with nv <= this
 #endif
-#ifndef MI_PAIR_SDOF_PD
-#define MI_PAIR_SDOF_PD 6   // DOF-loop prefetch depth (sdof_loop): 2 -> 0.1609 ms, 4 -> 0.1592 (A/B, round 3); 6: 0.1356 -> 0.1349 (round 4)
-#endif
-
-// S_c . f for DOF c: the free root's six DOFs have unit subspaces (linear x, y, z then angular
-// x, y, z: the P1 set-up below), so their dot product is one component of f (what dot6 with a
-// unit vector returns, up to the sign of a zero); the joint DOFs' from S_c in LDS
 typedef float pv2 __attribute__((ext_vector_type(2)));
 // J_r . u over the NV DOFs (u in LDS, uniform per half), in DOF order: the narrow and the wide
 // PGS form v_r the same way
@@ -176,12 +146,6 @@ MI_D float pk_jdot(const float (&J)[NVC], const float* u) {
     sfor<0, NV>([&](auto C) { v += J[C] * u[C]; });
     return v;
 }
-template <class TP, int c>
-MI_D float sdot(const float (&sv)[6], const float (&f)[6]) {
-    if constexpr (TP::nr == 6 && c < 6) return f[c < 3 ? 3 + c : c - 3];
-    else return dot6(sv, f);
-}
-constexpr int sdof_first_loaded(int nr) { return nr == 6 ? 6 : 0; }
 
 // J_r[c] of this lane's constraint row r (contact or limit), for every DOF c (lane = row)
 template <class TP>
@@ -324,8 +288,7 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
     // lane = DOF, coalesced), gravity at P1 and friction once ahead of the PGS sweeps
     static_assert(TP::kCT && TP::nv <= 32, "paired kernel: compiled topology, nv <= 32");
     const int lane = pair_l64() & 31;
-    const int N = st.N, L = m.L, D = m.D, nv = m.nv, nr = m.nr;
-    (void)N;
+    const int L = m.L, D = m.D, nv = m.nv, nr = m.nr;
     const float dt = p.dt;
     float* us = sm + t.s_us;
     float* rhs = sm + t.s_r;
@@ -375,42 +338,8 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
     }
     wave_sync();
     STAMP(2);
-    // ---- P3: bias + CRBA rows (lane = DOF)
-    if (lane < nv) {
-        const int k = lane, l = k < nr ? 0 : k - nr + 1;
-        float s[6], I[10], f[6], F[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) s[c] = Ss[6 * k + c];
-        {
-            const float4* rec = reinterpret_cast<const float4*>(aux) + 4 * l;
-            const float4 a0 = rec[0], a1 = rec[1], a2 = rec[2], a3 = rec[3];
-            I[0] = a0.x; I[1] = a0.y; I[2] = a0.z; I[3] = a0.w;
-            I[4] = a1.x; I[5] = a1.y; I[6] = a1.z; I[7] = a1.w;
-            I[8] = a2.x; I[9] = a2.y; F[0] = a2.z; F[1] = a2.w;
-            F[2] = a3.x; F[3] = a3.y; F[4] = a3.z; F[5] = a3.w;
-        }
-        inertia_mul(I, s, f);
-        float diag = dot6(s, f);
-        float r = -dot6(s, F);
-        if (k >= nr) {
-            float damp, arm;
-            if constexpr (TP::kEnvP) {
-                damp = ep[kEnvpDamping + k - nr];
-                arm = ep[kEnvpDamping + D + k - nr];
-            } else {
-                damp = mc.lf(MC_DAMP, l);
-                arm = mc.lf(MC_ARM, l);
-            }
-            diag += arm + dt * damp;
-            r += st.eff[sx(st, k - nr, i)] - damp * us[k];
-        }
-        rhs[k] = r;
-        sdof_loop<TP, MI_PAIR_SDOF_PD, false, sdof_first_loaded(TP::nr)>(Ss, nullptr, [&](auto J, const float (&sj)[6], float) {
-            constexpr int j = J;
-            Mx[k * nv + j] = sdot<TP, j>(sj, f);
-        });
-        Mx[k * nv + k] = diag;
-    }
+    // ---- P3: bias + CRBA rows (lane = DOF), shared with the one-env-per-wave kernel
+    phase_p3_bias_crba<Grp32, TP>(lane, i, D, nv, nr, dt, us, rhs, Mx, Ss, mc, t, st, aux, ep);
     wave_sync();
     STAMP(3);
     // ---- P4: register LTDL (lane = column), factor published to LDS
@@ -1402,62 +1331,9 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
     STAMP_END();
 }
 
-// Task layer of the paired kernel: wave_task_pre / wave_loco_post of mi_wave.hpp with the env
-// of this lane's half (lane = lane & 31; the half's lane 0 does the sequential parts).
-MI_D float pair_task_pre(const DevModel& m, const DevState& st, const DevTask& tp, int i,
-                         const float* actions, int64_t* reset_buf, int64_t* progress_buf,
-                         float* potentials, float* prev_potentials, float* actions_out) {
-#pragma clang fp contract(off)
-    const int lane = pair_l64() & 31, N = st.N, D = m.D, A = tp.A;
-    const bool flagged = reset_buf[i] != 0;      // half-uniform
-    mi_dr_env dre{};
-    if (tp.dr_act) dre = dr_begin(st, tp, 1, i, flagged);
-    if (flagged) {
-        const uint64_t gid = (uint64_t)(st.off + i);
-        const uint32_t cnt = st.reset_count[i];
-        const float pn = tp.dof_pos_noise, vn = tp.dof_vel_noise;
-        const float pw = (float)((double)pn - (double)(-pn));
-        const float vw = (float)((double)vn - (double)(-vn));
-        if (lane < D) {
-            const int j = lane;
-            float u[4];
-            uniform4(st.seed, gid, cnt, (uint32_t)(j >> 2), 0, u);
-            float v = tp.init_dof[j] + (pw * u[j & 3] + (-pn));
-            const float lo = m.lower[j + 1], hi = m.upper[j + 1];
-            if (lo < hi) { v = v < hi ? v : hi; v = v > lo ? v : lo; }
-            st.q[sx(st, j, i)] = v;
-            const int s = D + j;
-            uniform4(st.seed, gid, cnt, (uint32_t)(s >> 2), 0, u);
-            st.qd[sx(st, j, i)] = vw * u[s & 3] + (-vn);
-        }
-        if (lane < 3) st.root_pos[sx(st, lane, i)] = st.origins[(size_t)lane * N + i] + tp.init_root_pos[lane];
-        if (lane < 4) st.root_quat[sx(st, lane, i)] = tp.init_root_quat[lane];
-        if (lane < 6) st.root_vel[sx(st, lane, i)] = 0.0f;
-        if (lane == 0) {
-            float rp[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) rp[k] = st.origins[(size_t)k * N + i] + tp.init_root_pos[k];
-            float tx = tp.target[0] - rp[0], ty = tp.target[1] - rp[1];
-            float pot = -sqrtf(tx * tx + ty * ty + 0.0f * 0.0f) / tp.task_dt;
-            prev_potentials[i] = pot;
-            potentials[i] = pot;
-            st.reset_count[i] = cnt + 1;
-            reset_buf[i] = 0;
-            progress_buf[i] = 0;
-        }
-    }
-    float a = 0.0f;
-    if (lane < A) {
-        const int j = lane;
-        a = clampf(actions[(size_t)A * i + j], -tp.clip_actions, tp.clip_actions);
-        if (tp.dr_act) a = dr_col(st, tp, 1, dre, i, j, a);
-        if (actions_out) actions_out[(size_t)A * i + j] = a;
-        st.eff[sx(st, j, i)] = a * tp.gears[j] * tp.power_scale;
-    }
-    if (tp.dr_act && lane == 0) dr_store(st, 1, i, dre);
-    return a;
-}
-
+// Post-physics task layer of the paired kernel: wave_loco_post of mi_wave.hpp with the env of
+// this lane's half (lane = lane & 31; the half's lanes 0..2 do the sequential parts). The
+// pre-physics half is task_pre<Grp32> (mi_phase.hpp).
 MI_D void pair_loco_post(const DevModel& m, const WaveTabs& t, const DevState& st,
                          const DevTask& tp, int i, float* sm, float a_lane,
                          float* obs_out, float* obs_task, float* rew, int64_t* reset_buf,

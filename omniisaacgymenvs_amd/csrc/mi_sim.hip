@@ -787,7 +787,7 @@ __global__ __launch_bounds__(256) MI_WAVE_OCC void k_env_step_wave(const KParams
     STAMP_BEGIN();
     float a_lane = 0.0f;
     if (live)
-        a_lane = wave_task_pre(m, t, st, tp, i, actions, reset_buf, progress_buf, pot, prev, actions_out);
+        a_lane = task_pre<Grp64>(m, st, tp, i, actions, reset_buf, progress_buf, pot, prev, actions_out);
     stage_model_constants(t, smem);
     if (!live) return;
     STAMP(13);
@@ -920,7 +920,7 @@ __global__ __launch_bounds__(512) MI_PAIR_OCC void k_env_step_pair(const KParams
     STAMP_BEGIN();
     float a_lane = 0.0f;
     if (live)
-        a_lane = pair_task_pre(m, st, tp, i, actions, reset_buf, progress_buf, pot, prev, actions_out);
+        a_lane = task_pre<Grp32>(m, st, tp, i, actions, reset_buf, progress_buf, pot, prev, actions_out);
     stage_model_constants(t, smem);
     if (!live) return;
     STAMP(13);

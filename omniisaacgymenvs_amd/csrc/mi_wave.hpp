@@ -629,6 +629,12 @@ MI_D void wave_link_forward(const MC& mc, int nr, const WaveTabs& t, float* sm, 
     rec[3] = make_float4(F[2], F[3], F[4], F[5]);
 }
 
+}  // namespace mi
+
+#include "mi_phase.hpp"   // the phases this kernel and the paired one (mi_pair.hpp) share
+
+namespace mi {
+
 // One articulated substep of env i, executed by the whole 64-lane workgroup.
 // sm: this env's LDS region; gW: this env's global slab of W rows [max_rows][WNV].
 // load_state: read the env's state record from HBM (first substep of a launch; later ones
@@ -695,53 +701,8 @@ MI_D void wave_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
     }
     wave_sync();
     STAMP(2);   // P2
-    // ---- P3: bias + CRBA (lane k = dof k)
-    if (lane < nv) {
-        const int k = lane, l = k < nr ? 0 : k - nr + 1;
-        float s[6], I[10], f[6], F[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) s[c] = Ss[6 * k + c];
-        {
-            const float4* rec = reinterpret_cast<const float4*>(aux) + 4 * l;
-            const float4 a0 = rec[0], a1 = rec[1], a2 = rec[2], a3 = rec[3];
-            I[0] = a0.x; I[1] = a0.y; I[2] = a0.z; I[3] = a0.w;
-            I[4] = a1.x; I[5] = a1.y; I[6] = a1.z; I[7] = a1.w;
-            I[8] = a2.x; I[9] = a2.y; F[0] = a2.z; F[1] = a2.w;
-            F[2] = a3.x; F[3] = a3.y; F[4] = a3.z; F[5] = a3.w;
-        }
-        inertia_mul(I, s, f);
-        float diag = dot6(s, f);
-        float r = -dot6(s, F);
-        if (k >= nr) {
-            const float damp = mc.lf(MC_DAMP, l);
-            diag += mc.lf(MC_ARM, l) + dt * damp;
-            r += st.eff[sx(st, k - nr, i)] - damp * us[k];
-        }
-        rhs[k] = r;
-        if constexpr (TP::kCT) {
-            // row k of M~: S_j . f for every j, branch-free (uniform j: the S_j reads are LDS
-            // broadcasts). Only the ancestors of k are ever read (ct_load_columns masks the
-            // rest), so the other entries are written but dead; a lane-varying ancestor branch
-            // per j cost more than the 6 FMAs it skipped. The diagonal goes last.
-            sfor<0, TP::nv>([&](auto J) {
-                constexpr int j = J;
-                float sj[6];
-#pragma unroll
-                for (int c = 0; c < 6; ++c) sj[c] = Ss[6 * j + c];
-                Mx[k * nv + j] = dot6(sj, f);
-            });
-            Mx[k * nv + k] = diag;
-        } else {
-            Mx[k * nv + k] = diag;
-            for (int a = t.anc_start[k]; a < t.anc_start[k + 1]; ++a) {
-                const int j = t.anc_list[a];
-                float sj[6];
-#pragma unroll
-                for (int c = 0; c < 6; ++c) sj[c] = Ss[6 * j + c];
-                Mx[k * nv + j] = dot6(sj, f);
-            }
-        }
-    }
+    // ---- P3: bias + CRBA (lane k = dof k), shared with the paired kernel
+    phase_p3_bias_crba<Grp64, TP>(lane, i, D, nv, nr, dt, us, rhs, Mx, Ss, mc, t, st, aux, nullptr);
     wave_sync();
     STAMP(3);   // P3
     // ---- P4: LTDL in place (M = L^T D L, L strictly below the diagonal)
@@ -1587,73 +1548,13 @@ MI_D void wave_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
 // Wave-cooperative task layer of the fused env step (locomotion tasks). Same formulas, same
 // evaluation order and the same Philox streams as the one-lane versions in mi_task.hpp; the
 // work is spread over lanes (lane j = DOF j) and reads the LDS-resident physics state.
+// The pre-physics half is task_pre<Grp64> (mi_phase.hpp), shared with the paired kernel.
 // ---------------------------------------------------------------------------------------
-
-// VecEnvRLGames.step's clamp + action noise DR (vec_env_rlgames.py:57-60), then
-// pre_physics_step (locomotion.py:103-145): mask-driven reset_idx, efforts. Returns lane j's
-// action as pre_physics_step received it (task.actions[i, j]; 0 on lanes >= A).
-MI_D float wave_task_pre(const DevModel& m, const WaveTabs& t, const DevState& st,
-                         const DevTask& tp, int i, const float* actions, int64_t* reset_buf,
-                         int64_t* progress_buf, float* potentials, float* prev_potentials,
-                         float* actions_out) {
-#pragma clang fp contract(off)
-    const int lane = wave_lane(), N = st.N, D = m.D, A = tp.A;
-    const bool flagged = reset_buf[i] != 0;      // wave-uniform
-    mi_dr_env dre{};
-    if (tp.dr_act) dre = dr_begin(st, tp, 1, i, flagged);
-    if (flagged) {
-        const uint64_t gid = (uint64_t)(st.off + i);
-        const uint32_t cnt = st.reset_count[i];
-        const float pn = tp.dof_pos_noise, vn = tp.dof_vel_noise;
-        const float pw = (float)((double)pn - (double)(-pn));
-        const float vw = (float)((double)vn - (double)(-vn));
-        if (lane < D) {
-            const int j = lane;
-            float u[4];
-            uniform4(st.seed, gid, cnt, (uint32_t)(j >> 2), 0, u);
-            float v = tp.init_dof[j] + (pw * u[j & 3] + (-pn));
-            const float lo = m.lower[j + 1], hi = m.upper[j + 1];
-            if (lo < hi) { v = v < hi ? v : hi; v = v > lo ? v : lo; }
-            st.q[sx(st, j, i)] = v;
-            const int s = D + j;
-            uniform4(st.seed, gid, cnt, (uint32_t)(s >> 2), 0, u);
-            st.qd[sx(st, j, i)] = vw * u[s & 3] + (-vn);
-        }
-        if (lane < 3) {
-            const float rp = st.origins[(size_t)lane * N + i] + tp.init_root_pos[lane];
-            st.root_pos[sx(st, lane, i)] = rp;
-        }
-        if (lane < 4) st.root_quat[sx(st, lane, i)] = tp.init_root_quat[lane];
-        if (lane < 6) st.root_vel[sx(st, lane, i)] = 0.0f;
-        if (lane == 0) {
-            float rp[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) rp[k] = st.origins[(size_t)k * N + i] + tp.init_root_pos[k];
-            float tx = tp.target[0] - rp[0], ty = tp.target[1] - rp[1];
-            float pot = -sqrtf(tx * tx + ty * ty + 0.0f * 0.0f) / tp.task_dt;
-            prev_potentials[i] = pot;
-            potentials[i] = pot;
-            st.reset_count[i] = cnt + 1;
-            reset_buf[i] = 0;
-            progress_buf[i] = 0;
-        }
-    }
-    float a = 0.0f;
-    if (lane < A) {
-        const int j = lane;
-        a = clampf(actions[(size_t)A * i + j], -tp.clip_actions, tp.clip_actions);
-        if (tp.dr_act) a = dr_col(st, tp, 1, dre, i, j, a);
-        if (actions_out) actions_out[(size_t)A * i + j] = a;
-        st.eff[sx(st, j, i)] = a * tp.gears[j] * tp.power_scale;
-    }
-    if (tp.dr_act && lane == 0) dr_store(st, 1, i, dre);
-    return a;
-}
 
 // post_physics_step (rl_task.py:231-251 -> locomotion.py:80-101,173-183), observation noise
 // DR (vec_env_rlgames.py:70-71) and _process_data's obs clamp, from the final physics state the
 // last substep left in LDS. Writes the unclamped (noisy) row to obs_task (when given) and the
-// clamped row to obs_out. a_lane: lane j's task.actions entry (wave_task_pre).
+// clamped row to obs_out. a_lane: lane j's task.actions entry (task_pre).
 MI_D void wave_loco_post(const DevModel& m, const WaveTabs& t, const DevState& st,
                          const DevTask& tp, int i, float* sm, float a_lane,
                          float* obs_out, float* obs_task, float* rew, int64_t* reset_buf,
