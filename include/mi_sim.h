@@ -243,6 +243,43 @@ int mi_get_link_jacobian(mi_sim* sim, const int32_t* link_ids, const float* offs
  * layouts; the analytic cart-pole is computed from its link tree like any other fixed-base model.
  * No atomics: the outputs are the same bits on every run. */
 int mi_get_dynamics(mi_sim* sim, float* M, float* cor, float* grav, void* stream);
+/* --- mass-matrix solve view: ArticulationView.solve_mass_matrices / get_forward_dynamics /
+ *     get_task_space_inertias — products with the inverse of the joint-space inertia, the operation
+ *     computed torque (Mt^-1 (tau - c - g)) and operational-space control (J Mt^-1 J^T) need on top
+ *     of mi_get_dynamics and mi_get_link_jacobian ---
+ * Mt is M of mi_get_dynamics (the same statements) plus the diagonal of the chosen mode on the joint
+ * DOFs; it is factorised on the chip by the stepper's own tree LTDL (Mt = L^T D L over the DOF
+ * tree, no fill-in) and never written to memory. Armature and damping come from each env's record
+ * of the per-env parameter table (mi_set_env_params) when it exists, else from the model.
+ * A bare-M mode is deliberately not offered: the rigid-body M of a model whose 3-DOF joints are
+ * chains of massless links is nearly singular (Humanoid: condition number up to 4.7e7, smallest
+ * eigenvalue ~1e-6, so a float32 solve is off by 1e-3 relative), while the matrices below have
+ * condition numbers of 6.9e3 / 3.3e3 and solve to 4e-6 relative in float32.
+ * u, nv as for mi_get_link_jacobian. Like the other getters the calls issue deferred substeps, are
+ * stream-ordered, do not block the host and do not allocate (capturable; a captured call keeps
+ * reading the parameter table it was captured with). They only read the state (and the efforts).
+ * Every model mi_sim_create accepts, both state layouts; the analytic cart-pole goes through its
+ * link tree (its own stepper treats damping explicitly, so there MI_MASS_STEPPER differs from the
+ * matrix it inverts by dt * damping). Fixed summation order, no atomics: the same bits on every
+ * run and every graph replay. Errors: MI_E_NULL; MI_E_SHAPE for R < 1 or K outside [1, L];
+ * MI_E_ARG for a bad `which` or link id. */
+enum { MI_MASS_ARMATURE = 0,  /* M + diag(armature)               : continuous-time inertia   */
+       MI_MASS_STEPPER  = 1 };/* M + diag(armature + dt * damping): the matrix mi_sim_step inverts */
+
+/* out[n,r,:] = Mt^-1 rhs[n,r,:];  rhs, out [N,R,nv] device, R >= 1; out may alias rhs. */
+int mi_solve_mass(mi_sim* sim, int32_t which, const float* rhs, int32_t R, float* out, void* stream);
+
+/* acc [N,nv] = Mt^-1 (S^T tau - c - g - B u): tau [N,D] device, NULL = the efforts last set.
+ * B = joint damping (0 on root DOFs). With MI_MASS_STEPPER, u + dt*acc is the velocity one
+ * contact-free, limit-free substep produces (mi_sim_params.angular_damping aside). */
+int mi_get_forward_dynamics(mi_sim* sim, int32_t which, const float* tau, float* acc, void* stream);
+
+/* Frames as mi_get_link_jacobian (host link_ids[K], offsets[K,3]|NULL). Either output may be
+ * NULL, not both.  minv_jt [N,6K,nv] = rows Mt^-1 J_r^T;  lam_inv [N,6K,6K] = J Mt^-1 J^T
+ * (the inverse task-space inertia; [i][j] and [j][i] the same bits). The Jacobian rows are formed
+ * on the chip; nothing is read back from memory. */
+int mi_get_link_task_inertia(mi_sim* sim, int32_t which, const int32_t* link_ids, const float* offsets,
+                             int32_t K, float* minv_jt, float* lam_inv, void* stream);
 /* State mirrors: row-major copies of the articulation state in caller-owned device buffers, the
  * tensors ArticulationView getters hand out with clone=False (get_world_poses, get_velocities,
  * get_joint_positions / velocities, _physics_view.get_force_sensor_forces: locomotion.py:81-89;

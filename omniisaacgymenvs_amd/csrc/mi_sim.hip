@@ -22,6 +22,7 @@
 #include "mi_pair.hpp"
 #include "mi_link.hpp"
 #include "mi_dyn.hpp"
+#include "mi_msolve.hpp"
 
 using namespace mi;
 
@@ -1867,6 +1868,8 @@ static int create_finish(mi_sim* s, const mi_model_desc* md) {
         if ((rc = upload(s, s->nominal.data(), s->nominal.size(), &s->nominal_dev))) return rc;
     }
     if ((rc = sync_kparams(s))) return rc;
+    if (hipFuncSetAttribute((const void*)k_mass_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMsLdsLimit) != hipSuccess)
+        return fail(MI_E_HIP, "k_mass_solve: %zu B of LDS per workgroup refused", kMsLdsLimit);
     if (step_kernels_lds_limit(s, false))   // the EnvP kernels get theirs with the table (envp_ensure)
         return fail(MI_E_HIP, "wave kernels: %zu B of LDS per workgroup refused", s->lds_bytes);
     return MI_OK;
@@ -2154,6 +2157,56 @@ int mi_get_dynamics(mi_sim* s, float* M, float* cor, float* grav, void* stream) 
                        s->dm, s->ds, gv, M, cor, grav);
     LAUNCH_CHECK();
     return MI_OK;
+}
+
+// --- mass-matrix solve view (mi_msolve.hpp): Mt^-1 products; reads the state, the efforts and the
+// per-env parameter table (gravity, damping, armature) only ---
+static int mass_solve_launch(mi_sim* s, const char* fn, int32_t which, int op, const float* rhs, int R, float* out,
+                             float* lam, const LinkReq* rq, void* stream) {
+    if (which != MI_MASS_ARMATURE && which != MI_MASS_STEPPER)
+        return fail(MI_E_ARG, "%s: which=%d is neither MI_MASS_ARMATURE nor MI_MASS_STEPPER", fn, which);
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    if (s->dm.nv == 0) return MI_OK;               // a model without DOFs has empty outputs
+    DynGravity gv;
+    for (int c = 0; c < 3; ++c) gv.g[c] = s->sp.g[c];
+    gv.envp = s->envp;
+    gv.stride = s->envp_stride;
+    const int K = rq ? rq->K : 0;
+    MsArgs a{};
+    a.op = op; a.which = which; a.R = R;
+    a.VT = ms_tile_vectors(s->dm.L, s->dm.D, s->dm.nv, K, R);
+    a.dt = s->sp.dt;
+    a.rhs = rhs; a.out = out; a.lam = lam;
+    const size_t lds = MsLds(s->dm.L, s->dm.D, s->dm.nv, K, a.VT).bytes();
+    if (lds > kMsLdsLimit) return fail(MI_E_SHAPE, "%s: %zu B of LDS per workgroup", fn, lds);
+    static const LinkReq none{};
+    const dim3 grid((s->N + kMsEnvs - 1) / kMsEnvs);
+    hipLaunchKernelGGL(k_mass_solve, grid, dim3(kLinkThreads), lds, STREAM(stream), s->dm, s->ds, gv, a,
+                       rq ? *rq : none);
+    LAUNCH_CHECK();
+    return MI_OK;
+}
+
+int mi_solve_mass(mi_sim* s, int32_t which, const float* rhs, int32_t R, float* out, void* stream) {
+    NEED(s); NEED(rhs); NEED(out);
+    if (R < 1) return fail(MI_E_SHAPE, "mi_solve_mass: R=%d right-hand sides (expected >= 1)", R);
+    return mass_solve_launch(s, __func__, which, MS_SOLVE, rhs, R, out, nullptr, nullptr, stream);
+}
+
+int mi_get_forward_dynamics(mi_sim* s, int32_t which, const float* tau, float* acc, void* stream) {
+    NEED(s); NEED(acc);
+    return mass_solve_launch(s, __func__, which, MS_FD, tau, 1, acc, nullptr, nullptr, stream);
+}
+
+int mi_get_link_task_inertia(mi_sim* s, int32_t which, const int32_t* link_ids, const float* offsets, int32_t K,
+                             float* minv_jt, float* lam_inv, void* stream) {
+    NEED(s);
+    if (!minv_jt && !lam_inv) return fail(MI_E_NULL, "mi_get_link_task_inertia: minv_jt and lam_inv are both null");
+    LinkReq rq;
+    int rc = link_request(s, __func__, link_ids, offsets, K, &rq);
+    if (rc) return rc;
+    return mass_solve_launch(s, __func__, which, MS_TASK, nullptr, 6 * K, minv_jt, lam_inv, &rq, stream);
 }
 
 int mi_set_dof_efforts(mi_sim* s, const float* eff, const int32_t* idx, int32_t n, void* stream) {

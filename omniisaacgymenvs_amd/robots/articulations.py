@@ -290,6 +290,71 @@ class ArticulationView:
         """(M, c, g) of the three getters above from one launch."""
         return tuple(self._out(t, indices, clone) for t in self._dynamics(True, True, True))
 
+    # ---- mass-matrix solve view (include/mi_sim.h mi_solve_mass / mi_get_forward_dynamics /
+    # mi_get_link_task_inertia): products with the inverse of Mt = M + diag(armature [+ dt damping]),
+    # factorised on the chip by the stepper's tree LTDL. mode "stepper" is the matrix mi_sim_step
+    # inverts, "armature" the continuous-time inertia. Buffers as for the dynamics view: allocated
+    # on the first call of a shape and reused; clone=False hands out the buffer itself.
+    _MASS_MODES = {"armature": N.MI_MASS_ARMATURE, "stepper": N.MI_MASS_STEPPER}
+
+    @classmethod
+    def _mass_mode(cls, mode) -> int:
+        try:
+            return cls._MASS_MODES[mode]
+        except (KeyError, TypeError):
+            raise ValueError(f"mode {mode!r}: expected 'stepper' or 'armature'") from None
+
+    def _ms_buf(self, key, *shape) -> torch.Tensor:
+        if self.handle is None:
+            raise RuntimeError("the articulation view is not initialized")
+        bufs = self.__dict__.setdefault("_ms_bufs", {})
+        t = bufs.get((key, shape))
+        if t is None:
+            t = bufs[(key, shape)] = self._empty(*shape)
+        return t
+
+    def solve_mass_matrices(self, rhs: torch.Tensor, mode: str = "stepper", clone: bool = True) -> torch.Tensor:
+        """Mt^-1 rhs for rhs [count, nv] or [count, R, nv] (the result has rhs' shape)."""
+        which = self._mass_mode(mode)
+        nv = self.num_gen_vel
+        if rhs.dim() not in (2, 3) or rhs.shape[0] != self.count or rhs.shape[-1] != nv:
+            raise ValueError(f"rhs {tuple(rhs.shape)}: expected [{self.count}, {nv}] or [{self.count}, R, {nv}]")
+        r = self._f32(rhs)
+        R = 1 if r.dim() == 2 else int(r.shape[1])
+        out = self._ms_buf("solve", *r.shape)
+        rc = self._lib.mi_solve_mass(self.handle, which, r.data_ptr(), R, out.data_ptr(), self.stream())
+        if rc:
+            N.check(rc, "mi_solve_mass")
+        return out.clone() if clone else out
+
+    def get_forward_dynamics(self, efforts=None, mode: str = "stepper", indices=None, clone: bool = True) -> torch.Tensor:
+        """[count, nv] generalized accelerations Mt^-1 (S^T tau - c - g - B u) under the joint
+        efforts ``efforts`` [count, num_dof] (None: the efforts last set). With mode "stepper",
+        u + dt * acc is the velocity one contact-free, limit-free substep produces."""
+        which = self._mass_mode(mode)
+        tau = self._f32(efforts)
+        if tau is not None and tuple(tau.shape) != (self.count, self.num_dof):
+            raise ValueError(f"efforts {tuple(tau.shape)}: expected [{self.count}, {self.num_dof}]")
+        acc = self._ms_buf("fd", self.count, self.num_gen_vel)
+        rc = self._lib.mi_get_forward_dynamics(self.handle, which, N.ptr(tau), acc.data_ptr(), self.stream())
+        if rc:
+            N.check(rc, "mi_get_forward_dynamics")
+        return self._out(acc, indices, clone)
+
+    def get_task_space_inertias(self, body_names=None, mode: str = "stepper", clone: bool = True):
+        """(minv_jt [count, 6K, nv], lam_inv [count, 6K, 6K]) of the named bodies' frames (all
+        bodies by default): rows Mt^-1 J_r^T of the frames' Jacobian rows (get_jacobians' order),
+        and the inverse task-space inertia J Mt^-1 J^T, symmetric bit for bit."""
+        which = self._mass_mode(mode)
+        links, offs = self._frames(body_names)
+        K, nv = int(links.shape[0]), self.num_gen_vel
+        mj, lam = self._ms_buf("minv_jt", self.count, 6 * K, nv), self._ms_buf("lam_inv", self.count, 6 * K, 6 * K)
+        rc = self._lib.mi_get_link_task_inertia(self.handle, which, N.iptr(links), N.fptr(offs), K, mj.data_ptr(),
+                                                lam.data_ptr(), self.stream())
+        if rc:
+            N.check(rc, "mi_get_link_task_inertia")
+        return self._out(mj, None, clone), self._out(lam, None, clone)
+
     # ---- setters (indices: env ids, rows of the value tensors align with them) ----
     @staticmethod
     def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
