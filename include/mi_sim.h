@@ -280,6 +280,51 @@ int mi_get_forward_dynamics(mi_sim* sim, int32_t which, const float* tau, float*
  * on the chip; nothing is read back from memory. */
 int mi_get_link_task_inertia(mi_sim* sim, int32_t which, const int32_t* link_ids, const float* offsets,
                              int32_t K, float* minv_jt, float* lam_inv, void* stream);
+/* --- inverse-dynamics view: ArticulationView.get_inverse_dynamics / get_joint_reaction_wrenches,
+ *     RigidPrimView.get_accelerations, ArticulationView.get_coms / get_momenta /
+ *     get_centroidal_momentum_matrices / get_energies — the other direction of the two views above:
+ *     computed torque (tau = Mt acc + c + g + B u) by one recursive Newton-Euler pass that never
+ *     forms M, the frame bias acceleration Jdot u of operational-space control, and the whole-body
+ *     quantities balance controllers and imitation rewards are written in ---
+ * The three calls follow mi_get_dynamics' contract: they issue deferred substeps, are stream-ordered,
+ * do not block the host and do not allocate (capturable; a captured call keeps reading the parameter
+ * table it was captured with). They only read the state. Gravity, armature and damping come from each
+ * env's record of the per-env parameter table (mi_set_env_params) when it exists, else from
+ * mi_sim_params / the model. Every model mi_sim_create accepts, both state layouts; the analytic
+ * cart-pole goes through its link tree. Fixed summation order, no atomics: the same bits on every
+ * run and every graph replay. Any output may be NULL, not all of a call's (MI_E_NULL). u, nv as for
+ * mi_get_link_jacobian. */
+enum { MI_MASS_RIGID = 2 };   /* M alone: inverse dynamics only (harmless to multiply, unsafe to invert) */
+
+/* tau [N,nv] = Mt acc + c + g + B u   (acc [N,nv] device, NULL = 0)
+ *   MI_MASS_RIGID   : Mt = M, B = 0            -> M acc + cor + grav of mi_get_dynamics
+ *   MI_MASS_ARMATURE: Mt = M + diag(armature), B = joint damping
+ *   MI_MASS_STEPPER : Mt = M + diag(armature + dt damping), B = joint damping
+ * so mi_get_forward_dynamics(which, tau[:,joint dofs]) returns acc when the root entries of tau are 0.
+ * Root entries (floating base) are the wrench the world must apply at the root origin. acc = NULL
+ * gives the bits an all-zero acc gives. MI_E_ARG for any other `which`.
+ * joint_wrench [N,L,6]|NULL: (force, torque about link l's origin), world axes, that link l's
+ * parent (the world for link 0) transmits to link l for that motion under MI_MASS_RIGID terms
+ * (inertial + velocity-product - gravity forces of l's subtree; no armature, no damping):
+ * S_l . joint_wrench[l] == tau_rigid[dof of l]; joint_wrench[0] == tau_rigid[root] for a floating
+ * base, and is the base reaction for a fixed one. */
+int mi_get_inverse_dynamics(mi_sim* sim, int32_t which, const float* acc, float* tau, float* joint_wrench,
+                            void* stream);
+
+/* out [N,K,6] = J acc + Jdot u: time derivative of mi_get_link_state's vel for the same frames
+ * (classical linear acceleration of the frame origin, angular acceleration, world axes).
+ * acc NULL: the bias term Jdot u alone. Gravity does not enter. The frame (link 0, offset 0) of a
+ * floating root is acc[:, 0:6] itself. Errors as mi_get_link_state (host link_ids[K],
+ * offsets[K,3]|NULL; MI_E_SHAPE for K outside [1, L], MI_E_ARG for a bad link id); out NULL is
+ * MI_E_NULL. */
+int mi_get_link_acceleration(mi_sim* sim, const int32_t* link_ids, const float* offsets, int32_t K,
+                             const float* acc, float* out, void* stream);
+
+/* com [N,3] world; mom [N,6] = (total linear momentum, angular momentum about com), world axes;
+ * cmm [N,6,nv] with mom == cmm @ u (rows 0..2 / total mass == Jacobian of com);
+ * energy [N,2] = (1/2 u^T M u, -sum_l m_l gravity . com_l  [per-env gravity]). mom, cmm and the
+ * kinetic energy do not depend on where the env stands or on the parameter table. */
+int mi_get_momentum(mi_sim* sim, float* com, float* mom, float* cmm, float* energy, void* stream);
 /* State mirrors: row-major copies of the articulation state in caller-owned device buffers, the
  * tensors ArticulationView getters hand out with clone=False (get_world_poses, get_velocities,
  * get_joint_positions / velocities, _physics_view.get_force_sensor_forces: locomotion.py:81-89;

@@ -23,6 +23,7 @@
 #include "mi_link.hpp"
 #include "mi_dyn.hpp"
 #include "mi_msolve.hpp"
+#include "mi_idyn.hpp"
 
 using namespace mi;
 
@@ -2207,6 +2208,57 @@ int mi_get_link_task_inertia(mi_sim* s, int32_t which, const int32_t* link_ids, 
     int rc = link_request(s, __func__, link_ids, offsets, K, &rq);
     if (rc) return rc;
     return mass_solve_launch(s, __func__, which, MS_TASK, nullptr, 6 * K, minv_jt, lam_inv, &rq, stream);
+}
+
+// --- inverse-dynamics view (mi_idyn.hpp): RNEA torques and joint wrenches, frame accelerations,
+// momentum; reads the state and the per-env parameter table (gravity, damping, armature) only ---
+extern "C++" template <int OP>
+static int idyn_launch(mi_sim* s, IdArgs a, const LinkReq* rq, void* stream) {
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    DynGravity gv;
+    for (int c = 0; c < 3; ++c) gv.g[c] = s->sp.g[c];
+    gv.envp = s->envp;
+    gv.stride = s->envp_stride;
+    a.dt = s->sp.dt;
+    static const LinkReq none{};
+    const dim3 grid((s->N + kIdEnvs - 1) / kIdEnvs);
+    hipLaunchKernelGGL(k_inverse_dynamics<OP>, grid, dim3(kLinkThreads),
+                       IdLds(OP, s->dm.L, s->dm.D, s->dm.nv, rq ? rq->K : 0).bytes(), STREAM(stream), s->dm, s->ds, gv,
+                       a, rq ? *rq : none);
+    LAUNCH_CHECK();
+    return MI_OK;
+}
+
+int mi_get_inverse_dynamics(mi_sim* s, int32_t which, const float* acc, float* tau, float* joint_wrench,
+                            void* stream) {
+    NEED(s);
+    if (!tau && !joint_wrench) return fail(MI_E_NULL, "mi_get_inverse_dynamics: tau and joint_wrench are both null");
+    if (which != MI_MASS_ARMATURE && which != MI_MASS_STEPPER && which != MI_MASS_RIGID)
+        return fail(MI_E_ARG, "mi_get_inverse_dynamics: which=%d is not one of MI_MASS_ARMATURE, MI_MASS_STEPPER, MI_MASS_RIGID", which);
+    IdArgs a{};
+    a.which = which; a.acc = acc; a.tau = tau; a.wrench = joint_wrench;
+    return idyn_launch<ID_TAU>(s, a, nullptr, stream);
+}
+
+int mi_get_link_acceleration(mi_sim* s, const int32_t* link_ids, const float* offsets, int32_t K, const float* acc,
+                             float* out, void* stream) {
+    NEED(s);
+    if (!out) return fail(MI_E_NULL, "mi_get_link_acceleration: out is null");
+    LinkReq rq;
+    int rc = link_request(s, __func__, link_ids, offsets, K, &rq);
+    if (rc) return rc;
+    IdArgs a{};
+    a.acc = acc; a.out = out;
+    return idyn_launch<ID_ACC>(s, a, &rq, stream);
+}
+
+int mi_get_momentum(mi_sim* s, float* com, float* mom, float* cmm, float* energy, void* stream) {
+    NEED(s);
+    if (!com && !mom && !cmm && !energy) return fail(MI_E_NULL, "mi_get_momentum: com, mom, cmm and energy are all null");
+    IdArgs a{};
+    a.com = com; a.mom = mom; a.cmm = cmm; a.energy = energy;
+    return idyn_launch<ID_MOM>(s, a, nullptr, stream);
 }
 
 int mi_set_dof_efforts(mi_sim* s, const float* eff, const int32_t* idx, int32_t n, void* stream) {

@@ -84,6 +84,7 @@ class MiDrParams(C.Structure):
 MI_DR_OP_DIRECT = 2
 MI_ENVP_GRAVITY, MI_ENVP_FRICTION, MI_ENVP_DAMPING, MI_ENVP_ARMATURE = 0, 1, 2, 3
 MI_MASS_ARMATURE, MI_MASS_STEPPER = 0, 1
+MI_MASS_RIGID = 2        # mi_get_inverse_dynamics only
 
 
 class MiDrPhysSched(C.Structure):
@@ -127,6 +128,9 @@ _SIGS = {
     "mi_get_forward_dynamics": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_get_link_task_inertia": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _f32p, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
+    "mi_get_inverse_dynamics": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_get_link_acceleration": (C.c_int, [C.c_void_p, _i32p, _f32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_get_momentum": (C.c_int, [C.c_void_p] + [C.c_void_p] * 5),
     "mi_set_dof_efforts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "mi_set_dof_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                    C.c_void_p]),

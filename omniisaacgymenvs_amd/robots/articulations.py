@@ -355,6 +355,71 @@ class ArticulationView:
             N.check(rc, "mi_get_link_task_inertia")
         return self._out(mj, None, clone), self._out(lam, None, clone)
 
+    # ---- inverse-dynamics view (include/mi_sim.h mi_get_inverse_dynamics / mi_get_momentum): one
+    # recursive Newton-Euler launch, no mass matrix in memory. Buffers as for the solve view. mode
+    # "rigid" (M alone, no damping) exists for this direction only: M is harmless to multiply.
+    def _accelerations(self, accelerations) -> Optional[torch.Tensor]:
+        acc = self._f32(accelerations)
+        if acc is not None and tuple(acc.shape) != (self.count, self.num_gen_vel):
+            raise ValueError(f"accelerations {tuple(acc.shape)}: expected [{self.count}, {self.num_gen_vel}]")
+        return acc
+
+    def _inverse_dynamics(self, accelerations, mode, tau: bool, wrench: bool):
+        which = N.MI_MASS_RIGID if mode == "rigid" else self._mass_mode(mode)
+        acc = self._accelerations(accelerations)
+        t = self._ms_buf("id_tau", self.count, self.num_gen_vel) if tau else None
+        w = self._ms_buf("id_wrench", self.count, self.model.num_links, 6) if wrench else None
+        rc = self._lib.mi_get_inverse_dynamics(self.handle, which, N.ptr(acc), N.ptr(t), N.ptr(w), self.stream())
+        if rc:
+            N.check(rc, "mi_get_inverse_dynamics")
+        return t, w
+
+    def get_inverse_dynamics(self, accelerations=None, mode: str = "rigid", indices=None, clone: bool = True) -> torch.Tensor:
+        """[count, nv] generalized forces Mt acc + c + g + B u that produce the generalized
+        accelerations ``accelerations`` [count, nv] (None: zero). mode "rigid": Mt = M, B = 0, the
+        terms of get_dynamics; "armature" / "stepper": the matrices of get_forward_dynamics and
+        B = joint damping, so that call gives ``accelerations`` back from the joint entries."""
+        return self._out(self._inverse_dynamics(accelerations, mode, True, False)[0], indices, clone)
+
+    def get_joint_reaction_wrenches(self, accelerations=None, indices=None, clone: bool = True) -> torch.Tensor:
+        """[count, num_bodies, 6] (force, torque; world axes) that each body's parent transmits to it
+        through its joint for that motion: rigid-body terms only. The torque is taken about the
+        origin of the body's link (model.body_link: the last link of the body's joint chain, where
+        that joint sits). A copy: the library's rows are per link, the bodies' rows are picked."""
+        w = self._inverse_dynamics(accelerations, "rigid", False, True)[1]
+        links = getattr(self, "_body_link_t", None)
+        if links is None:
+            links = self._body_link_t = torch.as_tensor(np.asarray(self.model.body_link), device=self.device).long()
+        return (w if indices is None else w[indices.long()])[:, links]
+
+    def _momentum(self, com: bool, mom: bool, cmm: bool, energy: bool):
+        n, nv = self.count, self.num_gen_vel
+        b = [self._ms_buf(k, *shape) if on else None
+             for k, shape, on in (("com", (n, 3), com), ("mom", (n, 6), mom), ("cmm", (n, 6, nv), cmm),
+                                  ("energy", (n, 2), energy))]
+        rc = self._lib.mi_get_momentum(self.handle, *(N.ptr(t) for t in b), self.stream())
+        if rc:
+            N.check(rc, "mi_get_momentum")
+        return b
+
+    def get_coms(self, indices=None, clone: bool = True) -> torch.Tensor:
+        """[count, 3] world position of the articulation's centre of mass."""
+        return self._out(self._momentum(True, False, False, False)[0], indices, clone)
+
+    def get_momenta(self, indices=None, clone: bool = True) -> torch.Tensor:
+        """[count, 6]: total linear momentum, angular momentum about the centre of mass (world axes)."""
+        return self._out(self._momentum(False, True, False, False)[1], indices, clone)
+
+    def get_centroidal_momentum_matrices(self, indices=None, clone: bool = True) -> torch.Tensor:
+        """[count, 6, nv] with get_momenta() == cmm @ u; rows 0..2 / total mass are the Jacobian of
+        the centre of mass."""
+        return self._out(self._momentum(False, False, True, False)[2], indices, clone)
+
+    def get_energies(self, indices=None, clone: bool = True) -> torch.Tensor:
+        """[count, 2]: kinetic energy 1/2 u^T M u, potential energy -sum m_l gravity . com_l (each
+        env's own gravity when set_env_gravity gave it one)."""
+        return self._out(self._momentum(False, False, False, True)[3], indices, clone)
+
     # ---- setters (indices: env ids, rows of the value tensors align with them) ----
     @staticmethod
     def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -565,3 +630,19 @@ class RigidPrimView:
 
     def get_angular_velocities(self, indices=None, clone: bool = True) -> torch.Tensor:
         return self.get_velocities(indices, clone=False)[:, 3:].clone()
+
+    def get_accelerations(self, accelerations=None, indices=None, clone: bool = True) -> torch.Tensor:
+        """[N, K, 6] for the N envs of the articulation: classical linear acceleration of each body
+        origin and angular acceleration (world axes), J acc + Jdot u for the generalized
+        accelerations ``accelerations`` [N, nv] (None: the bias term Jdot u alone; gravity does not
+        enter). ``indices`` selects envs, the rows of ``accelerations``."""
+        a = self._art
+        if a is None:
+            raise RuntimeError(f"RigidPrimView {self.name!r} is not bound: ArticulationView.get_link_view(view)")
+        acc = a._accelerations(accelerations)
+        out = a._ms_buf(("link_acc", tuple(self._links), self._offs.tobytes()), a.count, self.num_bodies, 6)
+        rc = a._lib.mi_get_link_acceleration(a.handle, N.iptr(self._links), N.fptr(self._offs), self.num_bodies,
+                                             N.ptr(acc), out.data_ptr(), a.stream())
+        if rc:
+            N.check(rc, "mi_get_link_acceleration")
+        return ArticulationView._out(out, indices, clone)
