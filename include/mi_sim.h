@@ -528,6 +528,14 @@ int mi_sim_kernel_path(const mi_sim* sim, int32_t* path, int32_t* topology, int3
  * paths keep in LDS; a substep with more rows puts the rest in the env's global slab. 0 on the
  * one-lane-per-env path. */
 int mi_sim_w_rows_lds(const mi_sim* sim, int32_t* rows);
+/* Diagnostics (host only, no device): how the compiled wave kernels spread the composite sums of
+ * a substep (P2) over a group of `lanes` (32 or 64) lanes. The work items are the (link, slot)
+ * pairs, slot = one of the four float4 of a link's record; links ranked by descendant count,
+ * longest first, the items dealt to the lanes in passes. items[pass * lanes + lane] <- 4 link +
+ * slot, or -1 where the lane idles; passes <- the number of passes. items may be NULL (passes
+ * only); cap: entries items holds. link_parent as mi_model_desc.parent (root first, parent -1). */
+int mi_p2_item_table(const int32_t* link_parent, int32_t L, int32_t lanes, int32_t* items, int32_t cap,
+                     int32_t* passes);
 int mi_abi_version(void);
 /* SHA-256 (hex) of the sources this library was compiled from: csrc/mi_sim.hip, the csrc .hpp headers and
  * the include headers in name order (__graft_entry__.source_hash); "unknown" when built without it. A

@@ -275,6 +275,72 @@ MI_D void pair_wcol_w(const WSrc& ws, int g0, int kc, int nv, float (&wq)[4]) {
 }
 
 
+// ---- P2: composite inertia / force = the link's own record + its descendants' records, added in
+// descendant-list order (a left fold: the order of the additions is part of the result). Results
+// go to aux: Ic at 16 l, F at 16 l + 10.
+// lane = (link, slot) item of TP::p2 (mi_topo.hpp). A record's four float4 slots are independent
+// sums, so the root's fold is spread over four lanes and the short lists fill the other lanes,
+// instead of one lane per link walking four slots while the leaves' lanes idle. Each step of the
+// fold is a dependent pair of LDS reads (descendant id, then its slot), so the ids and the slots
+// are read kP2Batch at a time, the next batch's ids while this batch's slots are in flight: the
+// Humanoid root's 21 steps cost 7 LDS round trips instead of 42. The adds themselves stay one
+// chain per slot, in list order; indices past the end of a list are clamped to its last entry
+// (read, not added).
+// lane_here: everything a lane derives here (its links, slots and LDS addresses of up to three
+// passes) is the same in every substep, and the compiler otherwise computes it once ahead of the
+// substep loop and keeps it in registers through the whole kernel: 3-6 VGPRs spilled in the
+// Humanoid kernels, which have none to spare. Behind the opaque copy it is recomputed per
+// substep (a few VALU ops) and dead after P2.
+// The one-env-per-wave kernels keep lane = link.
+constexpr int kP2Batch = 4;
+// what the kernel decodes (word `pass` of the packed order, link lane >> 2 of it) is the table's
+// item (p2_item: what mi_p2_item_table hands to the host) for every pass and lane
+template <class TP>
+constexpr bool p2_decode_is_table() {
+    for (int p = 0; p < p2_passes(TP::L, 32); ++p)
+        for (int ln = 0; ln < 32; ++ln) {
+            const bool has = 8 * p + (ln >> 2) < TP::L;
+            const int it = has ? 4 * p2_unpack(TP::p2.pk[p], ln >> 2) + (ln & 3) : -1;
+            if (it != p2_item(TP::p2.pk, TP::L, 32, p, ln)) return false;
+        }
+    return true;
+}
+template <class TP>
+MI_D void pair_p2_composites(int lane, const MC& mc, const WaveTabs& t, const float* sm, float* aux) {
+    static_assert(p2_decode_is_table<TP>(), "P2 item decode");
+    constexpr int B = kP2Batch;
+    // native 4-vectors: each record sum is two v_pk_add_f32 per float4 (the same adds)
+    const pv4* recs = reinterpret_cast<const pv4*>(sm + t.s_F);
+    pv4* out = reinterpret_cast<pv4*>(aux);
+    const int* dl = mc.bi + t.mc_dsl;
+    const int ln = lane_here(lane) & 31;
+    const int slot = ln & 3, sub = ln >> 2;
+    sfor<0, p2_passes(TP::L, 32)>([&](auto P) {
+        constexpr int p = P;
+        const int l = p2_unpack(TP::p2.pk[p], sub);
+        if (8 * p + sub < TP::L) {
+            const int ds = mc.desc_start(l), de = mc.desc_start(l + 1);
+            pv4 a = recs[4 * l + slot];
+            int id[B];
+            if (ds < de) {
+#pragma unroll
+                for (int k = 0; k < B; ++k) id[k] = dl[min(ds + k, de - 1)];
+            }
+            for (int di = ds; di < de; di += B) {
+                pv4 r[B];
+#pragma unroll
+                for (int k = 0; k < B; ++k) r[k] = recs[4 * id[k] + slot];
+#pragma unroll
+                for (int k = 0; k < B; ++k) id[k] = dl[min(di + B + k, de - 1)];
+#pragma unroll
+                for (int k = 0; k < B; ++k)
+                    if (di + k < de) a += r[k];
+            }
+            out[4 * l + slot] = a;
+        }
+    });
+}
+
 // One articulated substep of the env of this lane's half (env i, LDS region sm, W slab gW).
 template <class TP>
 MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevState& st,
@@ -318,24 +384,9 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
     for (int l = lane; l < L; l += 32) wave_link_forward<TP::kEnvP>(mc, nr, t, sm, l, p, ep);
     wave_sync();
     STAMP(1);
-    // ---- P2: composite inertia / force
+    // ---- P2: composite inertia / force (lane = (link, slot) item)
     float* aux = sm + t.s_X;
-    {
-        // native 4-vectors: each record sum is two v_pk_add_f32 per float4 (the same adds)
-        const pv4* recs = reinterpret_cast<const pv4*>(sm + t.s_F);
-        for (int l = lane; l < L; l += 32) {
-            pv4 a0 = recs[4 * l], a1 = recs[4 * l + 1], a2 = recs[4 * l + 2], a3 = recs[4 * l + 3];
-            for (int di = mc.desc_start(l); di < mc.desc_start(l + 1); ++di) {
-                const int d = mc.desc(di);
-                a0 += recs[4 * d];
-                a1 += recs[4 * d + 1];
-                a2 += recs[4 * d + 2];
-                a3 += recs[4 * d + 3];
-            }
-            pv4* o = reinterpret_cast<pv4*>(aux) + 4 * l;
-            o[0] = a0; o[1] = a1; o[2] = a2; o[3] = a3;
-        }
-    }
+    pair_p2_composites<TP>(lane, mc, t, sm, aux);
     wave_sync();
     STAMP(2);
     // ---- P3: bias + CRBA rows (lane = DOF), shared with the one-env-per-wave kernel

@@ -1235,6 +1235,30 @@ int mi_debug_stamps_raw(unsigned long long* out, int slots) {
 #endif
 const char* mi_last_error(void) { return g_err.c_str(); }
 
+// the P2 item table of a link tree on a group of `lanes` lanes, as the compiled kernels decode it
+// (p2_link_order / p2_item, mi_topo.hpp): host only, no device
+int mi_p2_item_table(const int32_t* link_parent, int32_t L, int32_t lanes, int32_t* items, int32_t cap,
+                     int32_t* passes) {
+    if (!link_parent || !passes) return fail(MI_E_ARG, "mi_p2_item_table: NULL argument");
+    if (L < 1 || L > kP2MaxLinks || (lanes != 32 && lanes != 64))
+        return fail(MI_E_ARG, "mi_p2_item_table: L in 1..64, lanes 32 or 64");
+    if (link_parent[0] != -1) return fail(MI_E_ARG, "mi_p2_item_table: link 0 is the root (parent -1)");
+    for (int l = 1; l < L; ++l)
+        if (link_parent[l] < 0 || link_parent[l] >= l)
+            return fail(MI_E_ARG, "mi_p2_item_table: parents precede their children");
+    const int np = p2_passes(L, lanes);
+    *passes = np;
+    if (!items) return MI_OK;
+    if (cap < np * lanes) return fail(MI_E_ARG, "mi_p2_item_table: items holds fewer than passes * lanes entries");
+    int order[kP2MaxLinks], ndesc[kP2MaxLinks];
+    unsigned long long pk[kP2MaxLinks / 8];
+    p2_link_order(link_parent, L, order, ndesc);
+    p2_pack(order, L, pk);
+    for (int p = 0; p < np; ++p)
+        for (int ln = 0; ln < lanes; ++ln) items[p * lanes + ln] = p2_item(pk, L, lanes, p, ln);
+    return MI_OK;
+}
+
 // ---- mi_sim_create, stage by stage (each returns the error code; mi_sim_create destroys the
 // half-built sim on the first failure) ------------------------------------------------------
 // what a stage hands on to later ones (host side only)

@@ -173,6 +173,7 @@ _SIGS = {
     "mi_sim_nan_count": (C.c_int, [C.c_void_p, _i64p]),
     "mi_sim_kernel_path": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p]),
     "mi_sim_w_rows_lds": (C.c_int, [C.c_void_p, _i32p]),
+    "mi_p2_item_table": (C.c_int, [_i32p, C.c_int32, C.c_int32, _i32p, C.c_int32, _i32p]),
     "mi_abi_version": (C.c_int, []),
     "mi_build_id": (C.c_char_p, []),
     "mi_last_error": (C.c_char_p, []),
@@ -197,7 +198,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            if lenient and name == "mi_build_id":
+            if lenient and name in ("mi_build_id", "mi_p2_item_table"):
                 continue
             raise
         fn.restype = res
