@@ -325,6 +325,45 @@ int mi_get_link_acceleration(mi_sim* sim, const int32_t* link_ids, const float* 
  * energy [N,2] = (1/2 u^T M u, -sum_l m_l gravity . com_l  [per-env gravity]). mom, cmm and the
  * kinetic energy do not depend on where the env stands or on the parameter table. */
 int mi_get_momentum(mi_sim* sim, float* com, float* mom, float* cmm, float* energy, void* stream);
+/* --- contact view: RigidContactView over the articulation's bodies (foot-contact rewards, "knee
+ *     touched the ground" terminations, clearance shaping) and the contact Jacobian J_c a controller
+ *     needs next to mi_solve_mass (J_c Mt^-1 J_c^T) ---
+ * The contact set mi_sim_step would build from the CURRENT state, by the stepper's own definitions:
+ *  - ground candidates: the model's contact points, one per sphere and two per capsule, in geom
+ *    order; gap = root z + point z - radius against the plane z = 0, contact point (x, y, z -
+ *    radius), normal +z, friction directions +x, +y, second link -1;
+ *  - self candidates (enable_self_collisions and a model with pairs): the geom pairs in table
+ *    order through mi_pair_contact / mi_contact_basis of mi_geom.h; normal from B to A;
+ *  - a candidate is active when gap < contact_offset; `gap` is the surface gap (rest_offset not
+ *    subtracted); active ground candidates come first in candidate order, active pairs follow in
+ *    pair order, cut at (MI_MAX_ROWS - 3 ground - limited joints) / 3 (the budget above).
+ * The set differs from the one the stepper builds from the same state only for candidates whose gap
+ * is within rounding of contact_offset. Contact forces are not part of this view.
+ * C = max_contacts = min(candidates, MI_MAX_ROWS / 3) slots per env; slots at or above count[n] are
+ * written too: 0.0 in the float outputs, -1 in links. A model without geoms (Cartpole) has C = 0:
+ * only count (zeros) and clearance (+inf) are written.
+ * The three device calls follow the other views' contract: they issue deferred substeps, are
+ * stream-ordered, do not block the host and do not allocate (capturable). They only read the
+ * state. Every model mi_sim_create accepts, both state layouts. Compaction by ballot and prefix
+ * count in candidate order, no atomics: the same bits on every run and every graph replay. */
+int mi_get_contact_capacity(const mi_sim* sim, int32_t* max_contacts, int32_t* num_ground_candidates,
+                            int32_t* num_pairs);
+/* Any output may be NULL (skipped). count [N]; links [N,C,2] = (link of A, link of B or -1 for the
+ * ground); point [N,C,3] world; normal [N,C,3]; gap [N,C]. */
+int mi_get_contacts(mi_sim* sim, int32_t* count, int32_t* links, float* point, float* normal, float* gap,
+                    void* stream);
+/* J [N,C,3,nv]: rows (normal, t1, t2) of each slot; row . u = velocity of A's material point at the
+ * contact point minus B's, along that direction (the ground is B and at rest); u, nv as for
+ * mi_get_link_jacobian. Columns of DOFs above the common ancestor of A and B (the root's, for a
+ * self-contact) cancel and are exactly 0.0f, like those of DOFs that move neither body. J NULL is
+ * MI_E_NULL (with C = 0 there is nothing to write and the call returns 0). */
+int mi_get_contact_jacobian(mi_sim* sim, float* J, void* stream);
+/* Per link (host link_ids[K], 0 <= K <= L, else MI_E_SHAPE; an id outside [0, L) is MI_E_ARG):
+ * count [N,K] = kept contacts that involve the link (a self-contact counts for both of its links);
+ * clearance [N,K] = the smallest gap of any of the link's geoms, to the ground and to every geom it
+ * is paired with, active or not; +inf for a link without geoms. Either output may be NULL. */
+int mi_get_link_contact_summary(mi_sim* sim, const int32_t* link_ids, int32_t K, int32_t* count,
+                                float* clearance, void* stream);
 /* State mirrors: row-major copies of the articulation state in caller-owned device buffers, the
  * tensors ArticulationView getters hand out with clone=False (get_world_poses, get_velocities,
  * get_joint_positions / velocities, _physics_view.get_force_sensor_forces: locomotion.py:81-89;

@@ -24,6 +24,7 @@
 #include "mi_dyn.hpp"
 #include "mi_msolve.hpp"
 #include "mi_idyn.hpp"
+#include "mi_contact.hpp"
 
 using namespace mi;
 
@@ -113,6 +114,10 @@ struct mi_sim {
     void* pdr_desc = nullptr;         // PhysDR
     float* pdr_prm = nullptr;         // [4][4 + 2 D]: on_reset p0, p1, on_interval p0, p1
     uint32_t* pdr_state = nullptr;    // [4][N]: since, counter, epoch, draws
+    // contact view (mi_contact.hpp): the geom pairs the stepper tests (none with self-collision
+    // off), the contact capacity per env and the number of joints with a limit (row budget)
+    const int* ct_pairs = nullptr;
+    int ct_npairs = 0, ct_cap = 0, ct_nlimc = 0;
 };
 static hipError_t timed_launch(mi_sim* s, void* stream, hipEvent_t* ev0, hipEvent_t* ev1);
 static int flush_pending(mi_sim* s, void* stream);
@@ -1903,6 +1908,19 @@ static int create_finish(mi_sim* s, const mi_model_desc* md) {
 #undef UPW
 #undef AL
 
+// contact view (mi_contact.hpp): its own copy of the pair table (the wave path's lives in WaveTabs
+// and only there), the capacity and the budget's limit-row count, on every kernel path
+static int create_contact_view(mi_sim* s, const CreateCtx& cx) {
+    const mi_model_desc* md = cx.md;
+    s->ct_npairs = cx.self_on ? md->num_pairs : 0;
+    s->ct_cap = std::min(s->dm.npts + s->ct_npairs, MI_MAX_ROWS / 3);
+    s->ct_nlimc = 0;
+    for (int l = 1; l < s->dm.L; ++l) s->ct_nlimc += md->lower[l] < md->upper[l] ? 1 : 0;
+    std::vector<int> prs(2, 0);
+    if (s->ct_npairs) prs.assign(md->pairs, md->pairs + 2 * md->num_pairs);
+    return upload(s, prs.data(), prs.size(), &s->ct_pairs);
+}
+
 int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, int64_t off,
                   int32_t device_id, const float* env_origins, uint64_t seed, mi_sim** out) {
     if (!md || !prm || !out || !env_origins) return fail(MI_E_NULL, "mi_sim_create: null argument");
@@ -1930,6 +1948,7 @@ int mi_sim_create(const mi_model_desc* md, const mi_sim_params* prm, int32_t N, 
     if (!rc) rc = create_params(s, prm);   // (after the layout, which reads the solver-independent topology constants)
     if (!rc) rc = create_state(s, off, seed, env_origins);
     if (!rc) rc = create_finish(s, md);
+    if (!rc) rc = create_contact_view(s, cx);
     if (rc) {
         mi_sim_destroy(s);
         return rc;
@@ -2283,6 +2302,80 @@ int mi_get_momentum(mi_sim* s, float* com, float* mom, float* cmm, float* energy
     IdArgs a{};
     a.com = com; a.mom = mom; a.cmm = cmm; a.energy = energy;
     return idyn_launch<ID_MOM>(s, a, nullptr, stream);
+}
+
+// --- contact view (mi_contact.hpp): the stepper's contact set for the current state, its Jacobian
+// rows and a per-link summary; reads the state only, so the mirrors stay valid ---
+int mi_get_contact_capacity(const mi_sim* s, int32_t* max_contacts, int32_t* num_ground_candidates,
+                            int32_t* num_pairs) {
+    if (!s) return fail(MI_E_NULL, "null sim");
+    if (max_contacts) *max_contacts = s->ct_cap;
+    if (num_ground_candidates) *num_ground_candidates = s->dm.npts;
+    if (num_pairs) *num_pairs = s->ct_npairs;
+    return MI_OK;
+}
+
+extern "C++" template <int OP>
+static int contact_launch(mi_sim* s, CtArgs a, const LinkReq* rq, void* stream) {
+    const DevModel& m = s->dm;
+    const int K = rq ? rq->K : 0;
+    a.C = s->ct_cap; a.npairs = s->ct_npairs; a.nlimc = s->ct_nlimc; a.pairs = s->ct_pairs;
+    a.contact_offset = s->sp.contact_offset;
+    // the env tile shrinks until the workgroup's LDS fits (one env always does)
+    a.E = OP == CT_JAC ? kCtJacEnvs : kCtEnvs;
+    while (a.E > 1 && CtLds(OP, a.E, m.L, m.D, m.nv, a.C, K).bytes() > kCtLdsLimit) a.E >>= 1;
+    static const LinkReq none{};
+    const dim3 grid((s->N + a.E - 1) / a.E);
+    hipLaunchKernelGGL(k_contacts<OP>, grid, dim3(kCtThreads), CtLds(OP, a.E, m.L, m.D, m.nv, a.C, K).bytes(),
+                       STREAM(stream), s->dm, s->ds, a, rq ? *rq : none);
+    LAUNCH_CHECK();
+    return MI_OK;
+}
+
+int mi_get_contacts(mi_sim* s, int32_t* count, int32_t* links, float* point, float* normal, float* gap,
+                    void* stream) {
+    NEED(s);
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    if (s->ct_cap == 0) links = nullptr, point = normal = gap = nullptr;   // empty outputs
+    if (!count && !links && !point && !normal && !gap) return MI_OK;
+    CtArgs a{};
+    a.count = count; a.links = links; a.point = point; a.normal = normal; a.gap = gap;
+    return contact_launch<CT_DATA>(s, a, nullptr, stream);
+}
+
+int mi_get_contact_jacobian(mi_sim* s, float* J, void* stream) {
+    NEED(s);
+    const bool empty = s->ct_cap == 0 || s->dm.nv == 0;   // no contact slots or no DOFs: an empty Jacobian, nothing to write
+    if (!J && !empty) return fail(MI_E_NULL, "mi_get_contact_jacobian: J is null");
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    if (empty) return MI_OK;
+    CtArgs a{};
+    a.jac = J;
+    return contact_launch<CT_JAC>(s, a, nullptr, stream);
+}
+
+int mi_get_link_contact_summary(mi_sim* s, const int32_t* link_ids, int32_t K, int32_t* count, float* clearance,
+                                void* stream) {
+    NEED(s);
+    if (K < 0 || K > s->dm.L)
+        return fail(MI_E_SHAPE, "mi_get_link_contact_summary: K=%d links (expected 0..%d, the model's links)", K, s->dm.L);
+    if (K > 0 && !link_ids) return fail(MI_E_NULL, "mi_get_link_contact_summary: null link_ids");
+    for (int k = 0; k < K; ++k)
+        if (link_ids[k] < 0 || link_ids[k] >= s->dm.L)
+            return fail(MI_E_ARG, "mi_get_link_contact_summary: link_ids[%d]=%d is not a link (0..%d)", k, link_ids[k],
+                        s->dm.L - 1);
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    if (K == 0 || (!count && !clearance)) return MI_OK;
+    LinkReq rq;
+    memset(&rq, 0, sizeof rq);
+    rq.K = K;
+    for (int k = 0; k < K; ++k) rq.link[k] = link_ids[k];
+    CtArgs a{};
+    a.lcount = count; a.clearance = clearance;
+    return contact_launch<CT_SUMMARY>(s, a, &rq, stream);
 }
 
 int mi_set_dof_efforts(mi_sim* s, const float* eff, const int32_t* idx, int32_t n, void* stream) {

@@ -420,6 +420,75 @@ class ArticulationView:
         env's own gravity when set_env_gravity gave it one)."""
         return self._out(self._momentum(False, False, False, True)[3], indices, clone)
 
+    # ---- contact view (include/mi_sim.h mi_get_contacts / mi_get_contact_jacobian): the contact set
+    # the stepper would build from the current state. Buffers as for the solve view: allocated on
+    # the first call and reused; clone=False hands out the buffer itself.
+    def _contact_capacity(self):
+        cap = getattr(self, "_ct_cap", None)
+        if cap is None:
+            if self.handle is None:
+                raise RuntimeError("the articulation view is not initialized")
+            c, g, p = C.c_int32(), C.c_int32(), C.c_int32()
+            N.check(self._lib.mi_get_contact_capacity(self.handle, C.byref(c), C.byref(g), C.byref(p)),
+                    "mi_get_contact_capacity")
+            cap = self._ct_cap = (int(c.value), int(g.value), int(p.value))
+        return cap
+
+    @property
+    def max_contacts(self) -> int:
+        """C: contact slots per env (ground candidates + self-collision pairs, at most MI_MAX_ROWS / 3)."""
+        return self._contact_capacity()[0]
+
+    def _ct_ibuf(self, key, *shape) -> torch.Tensor:
+        bufs = self.__dict__.setdefault("_ms_bufs", {})
+        t = bufs.get((key, shape))
+        if t is None:
+            t = bufs[(key, shape)] = torch.empty(shape, dtype=torch.int32, device=self.device)
+        return t
+
+    def get_contact_data(self, indices=None, clone: bool = True):
+        """(count [N] int32, bodies [N, C, 2] int32, points [N, C, 3] world, normals [N, C, 3],
+        separations [N, C]) of the contacts the next physics step starts from: ground contacts first,
+        then self-contacts, ``count`` of the C = max_contacts slots filled (the others hold 0 and body
+        -1). ``bodies`` are body indices (body_names) of A and B, B = -1 for the ground; the normal
+        points from B to A; a separation is the surface gap (negative: penetration), below
+        contact_offset for every contact. One launch."""
+        n, c = self.count, self.max_contacts
+        cnt, lnk = self._ct_ibuf("ct_count", n), self._ct_ibuf("ct_links", n, c, 2)
+        pt, nr, gp = self._ms_buf("ct_point", n, c, 3), self._ms_buf("ct_normal", n, c, 3), self._ms_buf("ct_gap", n, c)
+        rc = self._lib.mi_get_contacts(self.handle, cnt.data_ptr(), lnk.data_ptr(), pt.data_ptr(), nr.data_ptr(),
+                                       gp.data_ptr(), self.stream())
+        if rc:
+            N.check(rc, "mi_get_contacts")
+        tab = getattr(self, "_link_body_t", None)
+        if tab is None:   # link -> index of the body it belongs to; the last entry serves link -1 (the ground)
+            m = self.model
+            ids = [m.get_body_index(m.body_of_link[l]) for l in range(m.num_links)] + [-1]
+            tab = self._link_body_t = torch.as_tensor(ids, dtype=torch.int32, device=self.device)
+        bodies = self._ct_ibuf("ct_bodies", n, c, 2)
+        torch.index_select(tab, 0, lnk.view(-1).long() % tab.shape[0], out=bodies.view(-1))
+        return tuple(self._out(t, indices, clone) for t in (cnt, bodies, pt, nr, gp))
+
+    def get_contact_jacobians(self, indices=None, clone: bool = True) -> torch.Tensor:
+        """[N, C, 3, nv]: rows (normal, tangent 1, tangent 2) of every contact slot of
+        get_contact_data; row @ u is the velocity of A's material point at the contact point minus
+        B's along that direction. Slots at and above the env's count are zero."""
+        J = self._ms_buf("ct_jac", self.count, self.max_contacts, 3, self.num_gen_vel)
+        rc = self._lib.mi_get_contact_jacobian(self.handle, J.data_ptr(), self.stream())
+        if rc:
+            N.check(rc, "mi_get_contact_jacobian")
+        return self._out(J, indices, clone)
+
+    def _link_contact_summary(self, links: np.ndarray, count: bool, clearance: bool):
+        n, K = self.count, int(links.shape[0])
+        key = tuple(int(x) for x in links)
+        cnt = self._ct_ibuf(("ct_lcount", key), n, K) if count else None
+        clr = self._ms_buf(("ct_clear", key), n, K) if clearance else None
+        rc = self._lib.mi_get_link_contact_summary(self.handle, N.iptr(links), K, N.ptr(cnt), N.ptr(clr), self.stream())
+        if rc:
+            N.check(rc, "mi_get_link_contact_summary")
+        return cnt, clr
+
     # ---- setters (indices: env ids, rows of the value tensors align with them) ----
     @staticmethod
     def _f32(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -646,3 +715,23 @@ class RigidPrimView:
         if rc:
             N.check(rc, "mi_get_link_acceleration")
         return ArticulationView._out(out, indices, clone)
+
+    # ---- contacts of the view's bodies (include/mi_sim.h mi_get_link_contact_summary): what the
+    # reference's tasks read from a RigidContactView — "does the foot touch", "did a knee hit the
+    # ground", clearance shaping. A body's geoms ride on its link (model.body_link).
+    def _contact_summary(self, count: bool, clearance: bool):
+        a = self._art
+        if a is None:
+            raise RuntimeError(f"RigidPrimView {self.name!r} is not bound: ArticulationView.get_link_view(view)")
+        return a._link_contact_summary(self._links, count, clearance)
+
+    def get_contact_counts(self, indices=None, clone: bool = True) -> torch.Tensor:
+        """[N, K] int32 for the N envs of the articulation: contacts of the set the next physics step
+        starts from (ArticulationView.get_contact_data) that involve each body, ground and
+        self-contacts alike. ``indices`` selects envs."""
+        return ArticulationView._out(self._contact_summary(True, False)[0], indices, clone)
+
+    def get_min_separations(self, indices=None, clone: bool = True) -> torch.Tensor:
+        """[N, K]: the smallest surface gap of any of each body's geoms, to the ground and to every geom
+        it may self-collide with, in contact or not; +inf for a body without geoms."""
+        return ArticulationView._out(self._contact_summary(False, True)[1], indices, clone)
