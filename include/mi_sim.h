@@ -271,7 +271,9 @@ int mi_solve_mass(mi_sim* sim, int32_t which, const float* rhs, int32_t R, float
 
 /* acc [N,nv] = Mt^-1 (S^T tau - c - g - B u): tau [N,D] device, NULL = the efforts last set.
  * B = joint damping (0 on root DOFs). With MI_MASS_STEPPER, u + dt*acc is the velocity one
- * contact-free, limit-free substep produces (mi_sim_params.angular_damping aside). */
+ * contact-free, limit-free substep produces (mi_sim_params.angular_damping aside). While a body
+ * wrench buffer exists (mi_apply_link_wrenches) its generalized force Q is part of the right-hand
+ * side, as in the step: Mt^-1 (S^T tau + Q - c - g - B u); without one the result is unchanged. */
 int mi_get_forward_dynamics(mi_sim* sim, int32_t which, const float* tau, float* acc, void* stream);
 
 /* Frames as mi_get_link_jacobian (host link_ids[K], offsets[K,3]|NULL). Either output may be
@@ -364,6 +366,42 @@ int mi_get_contact_jacobian(mi_sim* sim, float* J, void* stream);
  * is paired with, active or not; +inf for a link without geoms. Either output may be NULL. */
 int mi_get_link_contact_summary(mi_sim* sim, const int32_t* link_ids, int32_t K, int32_t* count,
                                 float* clearance, void* stream);
+/* --- body wrenches: RigidPrimView.apply_forces / apply_forces_and_torques_at_pos over the
+ *     articulation's bodies (rotor thrusts, tasks/quadcopter.py:159, crazyflie.py:261,
+ *     ingenuity.py:172; push perturbations; the `rigid_prim_views: force` randomization group) ---
+ * K frames as mi_get_link_state (HOST link_ids[K], offsets[K,3]|NULL = link origins). force, torque:
+ * DEVICE [n,K,3], either may be NULL (not both: MI_E_NULL); idx: device int64 [n]|NULL (rows 0..n-1;
+ * out-of-range ids are ignored, as mi_set_env_params; an id named twice in one call is undefined).
+ * is_global 1: world axes; 0: the link's axes at call time. accumulate 0: the envs named REPLACE
+ * their generalized force; 1: add to it.
+ * The call turns the wrenches into the generalized force Q[n] = sum_k J_k(n)^T (f_k, tau_k), J_k
+ * exactly mi_get_link_jacobian's frame Jacobian at the current state (its u and nv), formed on the
+ * chip, summed in call order k = 0..K-1 (no atomics: the same bits on every run), and stores it in a
+ * sim-owned [N,nv] buffer. Entries of DOFs that move none of the frames are exactly 0 (accumulate 0).
+ * From then on Q acts in EVERY substep as a constant generalized force, root DOFs included, like an
+ * effort: M~ (u+ - u) / dt = S^T tau + Q - c - g - B u. It is frozen in generalized coordinates at the
+ * configuration of the call and stays until it is replaced or cleared; a reset does not clear it
+ * (PhysX holds the world-frame force over the step and drops it afterwards; a
+ * task that re-applies every pre_physics_step, as the three above do, sees no difference beyond
+ * O(dt) per step).
+ * The first call allocates the buffer (zeros) and, if absent, the per-env parameter table with the
+ * nominal values (mi_set_env_params): the force is added by the kernel variants that read the
+ * table, so the physics is otherwise unchanged and the plain kernels know nothing of it. Hence the
+ * table's limits: MI_E_STATE on the wavefront-per-env path and for a first call inside a stream
+ * capture; MI_E_ARG for MI_DYN_CARTPOLE (the analytic cart-pole takes efforts only).
+ * mi_sim_clear_env_params drops the wrench buffer with the table.
+ * Like the other entry points the three calls issue deferred substeps first (those ran under the
+ * force of their request), are stream-ordered, do not block the host and allocate nothing after the
+ * first use (capturable). They do not write the state: the mirrors stay valid. Every articulated
+ * model mi_sim_create accepts, both state layouts. Errors: MI_E_SHAPE for K outside [1, L] or n < 0
+ * (n > N without idx); MI_E_ARG for a bad link id. */
+int mi_apply_link_wrenches(mi_sim* sim, const int32_t* link_ids, const float* offsets, int32_t K,
+                           const float* force, const float* torque, const int64_t* idx, int32_t n,
+                           int32_t is_global, int32_t accumulate, void* stream);
+/* Q rows of the envs named <- exact zeros (idx NULL, n = N: all). A no-op before the first wrench. */
+int mi_clear_link_wrenches(mi_sim* sim, const int64_t* idx, int32_t n, void* stream);
+/* Q [N,nv] device <- the generalized force in effect (zeros before any wrench was applied). */
+int mi_get_applied_generalized_forces(mi_sim* sim, float* Q, void* stream);
 /* State mirrors: row-major copies of the articulation state in caller-owned device buffers, the
  * tensors ArticulationView getters hand out with clone=False (get_world_poses, get_velocities,
  * get_joint_positions / velocities, _physics_view.get_force_sensor_forces: locomotion.py:81-89;
@@ -503,7 +541,9 @@ int mi_set_env_params(mi_sim* sim, int32_t attr, const float* values /*[n,dim] d
 /* Before the table exists: the nominal values broadcast over the envs. */
 int mi_get_env_params(mi_sim* sim, int32_t attr, float* out /*[N,dim] device*/, void* stream);
 /* Drops the table (and leaves the physics DR schedules off): back to the nominal physics and to
- * the kernels that know no table. Waits for the device. */
+ * the kernels that know no table. The body wrench buffer (mi_apply_link_wrenches) rides on the
+ * table's kernels and is dropped with it: no generalized force is in effect afterwards. Waits for
+ * the device. */
 int mi_sim_clear_env_params(mi_sim* sim);
 
 /* Physics DR schedules (include/mi_dr_phys.h): per attribute an optional on_reset and an optional

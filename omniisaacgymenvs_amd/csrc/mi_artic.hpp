@@ -109,10 +109,11 @@ MI_D void make_row(const DevModel& m, const WS& w, int r, int l, const float* f)
 
 // kEnvP: joint damping / armature from env i's record ep of the per-env parameter table
 // (include/mi_sim.h mi_set_env_params; layout: mi_topo.hpp); the caller passes the record's
-// gravity and friction in p.
+// gravity and friction in p. wq (kEnvP only, may be null): the body wrenches' generalized forces
+// [N][nv] (mi_wrench.hpp), added to every DOF's right-hand side; null: no add at all.
 template <bool kEnvP = false>
 MI_D void artic_substep(const DevModel& m, const DevState& st, const SimP& p, int i,
-                        const float* ep = nullptr) {
+                        const float* ep = nullptr, const float* wq = nullptr) {
     const int N = st.N, L = m.L, D = m.D, nv = m.nv, nr = m.nr;
     const float dt = p.dt;
     WS w(st.ws, m.slots, i);
@@ -270,6 +271,9 @@ MI_D void artic_substep(const DevModel& m, const DevState& st, const SimP& p, in
                 diag += m.armature[l] + dt * m.damping[l];
                 rhs += st.eff[sx(st, k - nr, i)] - m.damping[l] * w[m.o_u + k];
             }
+        }
+        if constexpr (kEnvP) {
+            if (wq) rhs += wq[(size_t)i * nv + k];
         }
         w[m.o_M + k * nv + k] = diag;
         w[m.o_r + k] = rhs;

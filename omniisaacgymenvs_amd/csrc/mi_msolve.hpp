@@ -45,6 +45,7 @@ struct MsArgs {
     const float* rhs;         // MS_SOLVE: [N,R,nv]; MS_FD: tau [N,D] or nullptr (the state's efforts)
     float* out;               // MS_SOLVE: out; MS_FD: acc; MS_TASK: minv_jt or nullptr
     float* lam;               // MS_TASK: lam_inv or nullptr
+    const float* wq;          // MS_FD: the body wrenches' generalized forces [N,nv] (mi_wrench.hpp) or nullptr
 };
 
 // LDS. Masks, the double inertias of the M path, cor / grav, state, ancestor lists (bytes), DOF axes
@@ -518,6 +519,7 @@ __global__ __launch_bounds__(kLinkThreads) void k_mass_solve(DevModel m, DevStat
                     const float tau = a.rhs ? a.rhs[(size_t)(e0 + e) * D + j] : st.eff[sx(st, j, e0 + e)];
                     val += tau - damp * se[e * SW + kLinkRootW + D + j];
                 }
+                if (a.wq) val += a.wq[(size_t)(e0 + e) * nv + c];
             } else {
                 const int row = v0 + v, k = row / 6;
                 val = link_jac_elem(colT + e * 6 * nv, sp + (e * K + k) * 3, kind, cm[k], nv, row - 6 * k, c);

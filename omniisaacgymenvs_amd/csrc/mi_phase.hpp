@@ -73,10 +73,14 @@ constexpr int sdof_first_loaded(int nr) { return nr == 6 ? 6 : 0; }
 // ---- P3: bias + CRBA (lane k = dof k)
 // ep (TP::kEnvP only): the env's record of the per-env parameter table, damping and armature
 // read where the state's effort line is (lane = DOF, coalesced)
+// wq (TP::kEnvP only, may be null): the body wrenches' generalized forces [N][nv]
+// (mi_wrench.hpp), env i's line read the same way and added to every DOF's bias, the root's
+// included; null (no wrench was ever applied): no add at all
 template <class G, class TP>
 MI_D void phase_p3_bias_crba(int lane, int i, int D, int nv, int nr, float dt, const float* us, float* rhs,
                              float* Mx, const float* Ss, const MC& mc, const WaveTabs& t,
-                             const DevState& st, const float* aux, const float* ep) {
+                             const DevState& st, const float* aux, const float* ep,
+                             const float* wq = nullptr) {
     if (lane < nv) {
         const int k = lane, l = k < nr ? 0 : k - nr + 1;
         float s[6], I[10], f[6], F[6];
@@ -104,6 +108,9 @@ MI_D void phase_p3_bias_crba(int lane, int i, int D, int nv, int nr, float dt, c
             }
             diag += arm + dt * damp;
             r += st.eff[sx(st, k - nr, i)] - damp * us[k];
+        }
+        if constexpr (TP::kEnvP) {
+            if (wq) r += wq[(size_t)i * nv + k];
         }
         rhs[k] = r;
         if constexpr (TP::kCT) {

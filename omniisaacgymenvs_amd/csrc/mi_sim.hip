@@ -25,6 +25,7 @@
 #include "mi_msolve.hpp"
 #include "mi_idyn.hpp"
 #include "mi_contact.hpp"
+#include "mi_wrench.hpp"
 
 using namespace mi;
 
@@ -106,6 +107,9 @@ struct mi_sim {
     // no table, the plain kernels run; else the EnvP / *_envp kernel variants
     float* envp = nullptr;
     int envp_stride = 0;
+    // body wrenches (mi_apply_link_wrenches): their generalized forces [N][nv], added to the bias by
+    // the EnvP / *_envp kernels; nullptr until the first wrench (and again after the table is dropped)
+    float* wq = nullptr;
     std::vector<float> nominal;       // the sim-wide values in record order [4 + 2 D]
     const float* nominal_dev = nullptr;
     // physics DR schedules (mi_sim_set_phys_dr): descriptor + per-component distribution
@@ -162,7 +166,8 @@ static void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipS
 // parameter table (include/mi_sim.h mi_set_env_params) instead of the sim-wide values
 template <bool kEnvP = false>
 __device__ __forceinline__ void physics_env(const DevModel& m, const DevState& st, const SimP& p,
-                                            int i, int substeps, const float* ep = nullptr) {
+                                            int i, int substeps, const float* ep = nullptr,
+                                            const float* wq = nullptr) {
     if constexpr (kEnvP) {
         // the record's scalars once per launch, in registers: the substeps see them as the sim's
         SimP pe = p;
@@ -174,7 +179,7 @@ __device__ __forceinline__ void physics_env(const DevModel& m, const DevState& s
             me.pole_damping = ep[kEnvpDamping + 1];
             physics_env<false>(me, st, pe, i, substeps);
         } else {
-            for (int s = 0; s < substeps; ++s) artic_substep<true>(m, st, pe, i, ep);
+            for (int s = 0; s < substeps; ++s) artic_substep<true>(m, st, pe, i, ep, wq);
         }
         return;
     }
@@ -196,10 +201,10 @@ __global__ void k_sim_step(DevModel m, DevState st, SimP p, int substeps) {
     physics_env(m, st, p, i, substeps);
 }
 __global__ void k_sim_step_envp(DevModel m, DevState st, SimP p, int substeps, const float* envp,
-                                int envp_stride) {
+                                int envp_stride, const float* wq) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= st.N) return;
-    physics_env<true>(m, st, p, i, substeps, envp + (size_t)i * envp_stride);
+    physics_env<true>(m, st, p, i, substeps, envp + (size_t)i * envp_stride, wq);
 }
 
 __global__ void k_pre_step(DevModel m, DevState st, DevTask tp, const float* actions,
@@ -421,11 +426,11 @@ __global__ void k_env_step_envp(DevModel m, DevState st, SimP p, DevTask tp, con
                                 int substeps, float* obs_out, float* obs_task, float* rew,
                                 int64_t* reset_buf, int64_t* progress_buf, float* pot, float* prev,
                                 float* actions_out, float* rew_out, int64_t* reset_out,
-                                const float* envp, int envp_stride) {
+                                const float* envp, int envp_stride, const float* wq) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= st.N) return;
     task_pre_env(m, st, tp, i, actions, reset_buf, progress_buf, pot, prev, actions_out, true);
-    physics_env<true>(m, st, p, i, substeps, envp + (size_t)i * envp_stride);
+    physics_env<true>(m, st, p, i, substeps, envp + (size_t)i * envp_stride, wq);
     MI_ENV_STEP_POST();
 }
 
@@ -444,6 +449,7 @@ struct KParams {
     // read by the EnvP instantiations only
     const float* envp;
     int envp_stride;
+    const float* wq;   // body wrenches' generalized forces [N][nv] or nullptr (EnvP instantiations only)
 };
 
 // launch with the model's compile-time topology (mi_topo_gen.hpp) or the runtime tables
@@ -487,7 +493,7 @@ static int sync_kparams(mi_sim* s) {
     if (!s->wave) return MI_OK;
     KParams h{};
     h.m = s->dm; h.t = s->wt; h.st = s->ds; h.p = s->sp; h.tp = s->tp; h.rows = s->rows;
-    h.envp = s->envp; h.envp_stride = s->envp_stride;
+    h.envp = s->envp; h.envp_stride = s->envp_stride; h.wq = s->wq;
     if (!s->kp_dev) {
         void* p = nullptr;
         int rc = dev_alloc(s, &p, sizeof(KParams));
@@ -883,9 +889,10 @@ __global__ __launch_bounds__(512) MI_PAIR_OCC void k_sim_step_pair(const KParams
     for (int s = 0; s < substeps; ++s) {
         const KParams* k = opaque_kp(kp);
         const float* ep = nullptr;         // env i's parameter record (the env the wave simulates,
-        if constexpr (T::kEnvP) ep = k->envp + (size_t)i * k->envp_stride;   // not its workgroup slot)
+        const float* wq = nullptr;         // not its workgroup slot) and the body wrenches' forces
+        if constexpr (T::kEnvP) { ep = k->envp + (size_t)i * k->envp_stride; wq = k->wq; }
         pair_artic_substep<T>(k->m, k->t, k->st, k->p, i, pair_wave(), smem, sm, gW, s == 0, s == substeps - 1,
-                              prio, load, ep);
+                              prio, load, ep, wq);
     }
     // World.step() then the getters (locomotion.py:81-89): the final state is still in LDS, so the
     // launch writes the getters' row-major mirrors itself (the same values it stored to the
@@ -938,9 +945,10 @@ __global__ __launch_bounds__(512) MI_PAIR_OCC void k_env_step_pair(const KParams
     for (int s = 0; s < substeps; ++s) {
         const KParams* k = opaque_kp(kp);
         const float* ep = nullptr;         // env i's parameter record (the env the wave simulates,
-        if constexpr (T::kEnvP) ep = k->envp + (size_t)i * k->envp_stride;   // not its workgroup slot)
+        const float* wq = nullptr;         // not its workgroup slot) and the body wrenches' forces
+        if constexpr (T::kEnvP) { ep = k->envp + (size_t)i * k->envp_stride; wq = k->wq; }
         pair_artic_substep<T>(k->m, k->t, k->st, k->p, i, pair_wave(), smem, sm, gW, s == 0, s == substeps - 1,
-                              prio, load, ep);
+                              prio, load, ep, wq);
     }
     STAMP_RESET();
     pair_loco_post(m, t, st, tp, i, sm, a_lane, obs_out, obs_task, rew, reset_buf, progress_buf,
@@ -2045,7 +2053,7 @@ static int launch_sim(mi_sim* s, int substeps, hipStream_t stream) {
             launch(V.sim, wave_grid(s), wave_block(s), s->lds_bytes, stream, nullptr, nullptr, kp, substeps);
         } else if constexpr (decltype(V)::kEnvP) {
             launch(V.sim, grid_for(s, s->N), dim3(s->block), 0, stream, nullptr, nullptr, s->dm, s->ds, s->sp,
-                   substeps, s->envp, s->envp_stride);
+                   substeps, s->envp, s->envp_stride, s->wq);
         } else {
             launch(V.sim, grid_for(s, s->N), dim3(s->block), 0, stream, nullptr, nullptr, s->dm, s->ds, s->sp,
                    substeps);
@@ -2222,6 +2230,7 @@ static int mass_solve_launch(mi_sim* s, const char* fn, int32_t which, int op, c
     a.VT = ms_tile_vectors(s->dm.L, s->dm.D, s->dm.nv, K, R);
     a.dt = s->sp.dt;
     a.rhs = rhs; a.out = out; a.lam = lam;
+    a.wq = op == MS_FD ? s->wq : nullptr;
     const size_t lds = MsLds(s->dm.L, s->dm.D, s->dm.nv, K, a.VT).bytes();
     if (lds > kMsLdsLimit) return fail(MI_E_SHAPE, "%s: %zu B of LDS per workgroup", fn, lds);
     static const LinkReq none{};
@@ -2734,7 +2743,7 @@ int mi_env_step(mi_sim* s, const float* actions, int32_t substeps, float* obs_ou
         else if constexpr (decltype(V)::kEnvP)
             launch(V.env, grid_for(s, s->N), dim3(s->block), 0, STREAM(stream), ev0, ev1, s->dm, s->ds, s->sp,
                    s->tp, actions, substeps, obs_out, obs_task, rew, reset_buf, progress_buf, potentials,
-                   prev_potentials, actions_out, rew_out, reset_out, s->envp, s->envp_stride);
+                   prev_potentials, actions_out, rew_out, reset_out, s->envp, s->envp_stride, s->wq);
         else
             launch(V.env, grid_for(s, s->N), dim3(s->block), 0, STREAM(stream), ev0, ev1, s->dm, s->ds, s->sp,
                    s->tp, actions, substeps, obs_out, obs_task, rew, reset_buf, progress_buf, potentials,
@@ -2912,7 +2921,69 @@ int mi_sim_clear_env_params(mi_sim* s) {
     free_tracked(s, s->envp);
     s->envp = nullptr;
     s->envp_stride = 0;
+    free_tracked(s, s->wq);   // the body wrenches ride on the table's kernels
+    s->wq = nullptr;
     return sync_kparams(s);
+}
+
+// ---- body wrenches (mi_wrench.hpp) ---------------------------------------------------------
+// The generalized-force buffer on first use, and the parameter table its kernels need.
+static int wrench_ensure(mi_sim* s, hipStream_t stream, const char* fn) {
+    if (s->dm.dyn == MI_DYN_CARTPOLE)
+        return fail(MI_E_ARG, "%s: the analytic cart-pole takes joint efforts only (no body wrenches)", fn);
+    if (int rc = envp_ensure(s, stream, fn)) return rc;
+    if (s->wq) return MI_OK;
+    if (capturing(stream)) return fail(MI_E_STATE, "%s: the first call allocates the wrench buffer: make it before the capture", fn);
+    void* p = nullptr;
+    if (int rc = dev_alloc(s, &p, sizeof(float) * (size_t)s->N * (size_t)std::max(1, s->dm.nv))) return rc;   // zeros
+    HIP_TRY(hipDeviceSynchronize());   // first use only: the zeros are in place on every stream
+    s->wq = (float*)p;
+    return sync_kparams(s);
+}
+
+int mi_apply_link_wrenches(mi_sim* s, const int32_t* link_ids, const float* offsets, int32_t K, const float* force,
+                           const float* torque, const int64_t* idx, int32_t n, int32_t is_global, int32_t accumulate,
+                           void* stream) {
+    NEED(s);
+    if (!force && !torque) return fail(MI_E_NULL, "mi_apply_link_wrenches: force and torque are both null");
+    LinkReq rq;
+    if (int rc = link_request(s, __func__, link_ids, offsets, K, &rq)) return rc;
+    if (n < 0 || (!idx && n > s->N)) return fail(MI_E_SHAPE, "%s: n %d out of range", __func__, n);
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);      // deferred substeps ran under the force of their request
+    if (int rc = wrench_ensure(s, STREAM(stream), __func__)) return rc;
+    if (n == 0 || s->dm.nv == 0) return MI_OK;
+    WrenchArgs a{};
+    a.n = n; a.is_global = is_global != 0; a.accumulate = accumulate != 0;
+    a.force = force; a.torque = torque; a.idx = idx; a.Q = s->wq;
+    const dim3 grid((n + kWrenchEnvs - 1) / kWrenchEnvs);
+    hipLaunchKernelGGL(k_apply_wrench, grid, dim3(kLinkThreads), wrench_lds(s->dm.D, s->dm.nv, K), STREAM(stream),
+                       s->dm, s->ds, rq, a);
+    LAUNCH_CHECK();
+    return MI_OK;
+}
+
+int mi_clear_link_wrenches(mi_sim* s, const int64_t* idx, int32_t n, void* stream) {
+    NEED(s);
+    if (n < 0 || (!idx && n > s->N)) return fail(MI_E_SHAPE, "%s: n %d out of range", __func__, n);
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    if (!s->wq || n == 0 || s->dm.nv == 0) return MI_OK;
+    hipLaunchKernelGGL(k_wrench_clear, dim3((unsigned)(((int64_t)n * s->dm.nv + 255) / 256)), dim3(256), 0,
+                       STREAM(stream), s->wq, s->dm.nv, idx, n, s->N);
+    LAUNCH_CHECK();
+    return MI_OK;
+}
+
+int mi_get_applied_generalized_forces(mi_sim* s, float* Q, void* stream) {
+    NEED(s); NEED(Q);
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    const size_t bytes = sizeof(float) * (size_t)s->N * (size_t)s->dm.nv;
+    if (bytes == 0) return MI_OK;
+    if (s->wq) HIP_TRY(hipMemcpyAsync(Q, s->wq, bytes, hipMemcpyDeviceToDevice, STREAM(stream)));
+    else HIP_TRY(hipMemsetAsync(Q, 0, bytes, STREAM(stream)));
+    return MI_OK;
 }
 
 int mi_sim_set_phys_dr(mi_sim* s, const mi_dr_phys_params* dr) {

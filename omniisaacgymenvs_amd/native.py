@@ -135,6 +135,10 @@ _SIGS = {
     "mi_get_contacts": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6),
     "mi_get_contact_jacobian": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_get_link_contact_summary": (C.c_int, [C.c_void_p, _i32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_apply_link_wrenches": (C.c_int, [C.c_void_p, _i32p, _f32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "mi_clear_link_wrenches": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mi_get_applied_generalized_forces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_set_dof_efforts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "mi_set_dof_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                    C.c_void_p]),

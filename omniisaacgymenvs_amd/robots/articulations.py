@@ -563,6 +563,56 @@ class ArticulationView:
     def set_velocities(self, velocities: torch.Tensor, indices=None) -> None:
         self._set_root_state(None, None, self._f32(velocities), indices)
 
+    # ---- body wrenches (include/mi_sim.h mi_apply_link_wrenches): forces and torques on bodies become
+    # one generalized force Q [count, nv] that every later substep applies like an effort, the root's
+    # six DOFs included, until it is replaced or cleared (a reset keeps it). Applied through link views
+    # (RigidPrimView.apply_forces / apply_forces_and_torques_at_pos). The first application allocates
+    # the sim's buffers: make it before capturing a graph.
+    def _apply_link_wrenches(self, links, offs, forces, torques, indices, is_global: bool, accumulate: bool) -> None:
+        idx, n = self._idx(indices, torch.int64)
+        if n == 0:
+            return
+        K = int(links.shape[0])
+        f, t = self._f32(forces), self._f32(torques)
+        for name, v in (("forces", f), ("torques", t)):
+            if v is not None and v.numel() != n * K * 3:       # the kernel trusts the shape
+                raise ValueError(f"{name} {tuple(v.shape)}: expected {n} envs x {K} bodies x 3")
+        rc = self._lib.mi_apply_link_wrenches(self.handle, N.iptr(links), N.fptr(offs), K, N.ptr(f), N.ptr(t),
+                                              None if idx is None else idx.data_ptr(), n, int(bool(is_global)),
+                                              int(bool(accumulate)), self.stream())
+        if rc:
+            N.check(rc, "mi_apply_link_wrenches")
+
+    def _wrench_accumulates(self, view) -> bool:
+        """Several link views applying in one step add up (Crazyflie's four rotor views); a view that
+        applies again starts the next step's round and replaces."""
+        seen = self.__dict__.setdefault("_wrench_round", set())
+        if id(view) in seen:
+            seen.clear()
+        acc = bool(seen)
+        seen.add(id(view))
+        return acc
+
+    def get_applied_generalized_forces(self, indices=None, clone: bool = True) -> torch.Tensor:
+        """[count, nv] generalized force of the body wrenches in effect (zeros before any was applied):
+        sum over the bodies of J^T (force, torque), J of get_jacobians at the time of the application."""
+        out = self._ms_buf("wrench_q", self.count, self.num_gen_vel)
+        rc = self._lib.mi_get_applied_generalized_forces(self.handle, out.data_ptr(), self.stream())
+        if rc:
+            N.check(rc, "mi_get_applied_generalized_forces")
+        return self._out(out, indices, clone)
+
+    def clear_body_wrenches(self, indices=None) -> None:
+        """No body wrench acts on the envs ``indices`` (all by default) from the next substep on."""
+        idx, n = self._idx(indices, torch.int64)
+        if indices is None:
+            self.__dict__.setdefault("_wrench_round", set()).clear()
+        if n == 0:
+            return
+        rc = self._lib.mi_clear_link_wrenches(self.handle, None if idx is None else idx.data_ptr(), n, self.stream())
+        if rc:
+            N.check(rc, "mi_clear_link_wrenches")
+
     # ---- per-env physics parameters (include/mi_sim.h mi_set_env_params) ----
     # The values omni.replicator.isaac's physics_view randomizes through the PhysX views
     # (randomize.py:308-430): gravity (SimulationContext), one friction coefficient per env
@@ -653,8 +703,8 @@ class RigidPrimView:
     K bodies in each of N envs are ``count = N K`` prims, env-major, so callers can
     ``.view(N, K, ...)``. Every getter is one mi_get_link_state launch on torch's current stream.
     The view owns its output tensors and hands them out like the state mirrors: with clone=False
-    the buffer itself, which the next read overwrites. Read-only: bodies are moved through their
-    articulation. Built by ``ArticulationView.get_link_view(body_names)``, or the reference's way,
+    the buffer itself, which the next read overwrites. Bodies are moved through their articulation;
+    apply_forces / apply_forces_and_torques_at_pos push on them. Built by ``ArticulationView.get_link_view(body_names)``, or the reference's way,
     ``RigidPrimView(prim_paths_expr=".../<Robot>/<body>", name=...)``, then bound with
     ``ArticulationView.get_link_view(view)``."""
 
@@ -715,6 +765,50 @@ class RigidPrimView:
         if rc:
             N.check(rc, "mi_get_link_acceleration")
         return ArticulationView._out(out, indices, clone)
+
+    # ---- forces on the view's bodies (include/mi_sim.h mi_apply_link_wrenches): the reference's
+    # RigidPrimView.apply_forces (quadcopter.py:159, crazyflie.py:261, ingenuity.py:172) and
+    # apply_forces_and_torques_at_pos, omni.isaac.core's signatures. ``indices`` are env ids (a view
+    # of one body per env, as the reference's rotor views are, has one prim per env); forces and
+    # torques are [n, K, 3] for the n envs named (or [n K, 3] env-major, or [n, 3] for K = 1).
+    # The wrench becomes a generalized force at the current configuration and acts on every substep
+    # until a view applies again (ArticulationView.clear_body_wrenches removes it); views that apply
+    # one after the other in the same step add up. ``accumulate`` overrides that rule.
+    def apply_forces_and_torques_at_pos(self, forces=None, torques=None, positions=None, indices=None,
+                                        is_global: bool = True, accumulate: Optional[bool] = None) -> None:
+        """``positions`` [K, 3] (or [n, K, 3] with identical rows): where the forces act, as offsets
+        from the body origins in the body's axes. Positions that differ per env are folded into the
+        torque in torch before the call (force at the origin + r x f)."""
+        a = self._art
+        if a is None:
+            raise RuntimeError(f"RigidPrimView {self.name!r} is not bound: ArticulationView.get_link_view(view)")
+        if forces is None and torques is None:
+            raise ValueError("apply_forces_and_torques_at_pos: forces and torques are both None")
+        K = self.num_bodies
+        shape = lambda v: None if v is None else torch.as_tensor(v, device=a.device).to(torch.float32).reshape(-1, K, 3)
+        f, t = shape(forces), shape(torques)
+        offs = self._offs
+        if positions is not None and f is not None:
+            p = torch.as_tensor(positions, device=a.device).to(torch.float32).reshape(-1, K, 3)
+            if p.shape[0] == 1 or bool((p == p[:1]).all()):
+                offs = np.ascontiguousarray(self._offs + p[0].cpu().numpy(), dtype=np.float32)
+            else:
+                r = p
+                if is_global:       # the offsets turned into world axes by the bodies' orientations
+                    quat = self.get_world_poses(clone=False)[1].view(a.count, K, 4)
+                    if indices is not None:
+                        quat = quat[torch.as_tensor(indices, device=a.device).long()]
+                    w, v = quat[..., :1], quat[..., 1:]
+                    c = torch.cross(v, r, dim=-1)
+                    r = r + 2.0 * (w * c + torch.cross(v, c, dim=-1))
+                rf = torch.cross(r, f, dim=-1)
+                t = rf if t is None else t + rf
+        acc = a._wrench_accumulates(self) if accumulate is None else bool(accumulate)
+        a._apply_link_wrenches(self._links, offs, f, t, indices, is_global, acc)
+
+    def apply_forces(self, forces, indices=None, is_global: bool = True) -> None:
+        """Forces at the body origins (RigidPrimView.apply_forces)."""
+        self.apply_forces_and_torques_at_pos(forces=forces, indices=indices, is_global=is_global)
 
     # ---- contacts of the view's bodies (include/mi_sim.h mi_get_link_contact_summary): what the
     # reference's tasks read from a RigidContactView — "does the foot touch", "did a knee hit the
