@@ -88,8 +88,10 @@ MI_D int pmax(int v) { return max(__builtin_amdgcn_readlane(v, 0), __builtin_amd
 // sum over each 32-lane half, returned to every lane of the half
 MI_D float psum(float v) { return pbc(half_sums(v), 31); }
 
-// in-register tree LTDL (ct_ltdl: the same statement, see there for what is kept exact and what
-// is left as junk) with per-half broadcasts; lane c of each half returns 1 / D_c. The junk above
+// in-register tree LTDL with per-half broadcasts: the arithmetic of ct_ltdl (see there for what is
+// kept exact and what is left as junk), the ancestor updates two per packed FMA where CtPkTab
+// pairs them (ct_ltdl itself stays scalar: its multipliers are v_readlane results in SGPRs);
+// lane c of each half returns 1 / D_c. The junk above
 // the diagonal differs per column and per env, but stays in its own half's lanes (pbcc reads the
 // lane's own half) and in entries nothing reads
 template <class T>
@@ -102,9 +104,22 @@ MI_D float ct_ltdl_pair(int lane, float (&Mc)[T::nvc]) {
         const int ln = lane_here(lane);
         const float inv = __builtin_amdgcn_rcpf(pbcc<k>(Mc[k]));
         const float t = Mc[k] * inv;
-        sfor<T::dof.anc_start[k], T::dof.anc_start[k + 1]>([&](auto A) {
-            constexpr int ii = T::dof.anc[A];
-            Mc[ii] -= pbcc<ii>(t) * Mc[k];
+        // two ancestors' updates per v_pk_fma_f32 where the list holds 2m + 1 and 2m (CtPkTab:
+        // the same fused multiply-add per element; the broadcasts as before)
+        using PK = CtPkTab<T>;
+        constexpr int a0 = T::dof.anc_start[k];
+        const pv2 mk2 = {Mc[k], Mc[k]};
+        sfor<0, T::dof.anc_start[k + 1] - a0>([&](auto A) {
+            constexpr int ii = T::dof.anc[a0 + A];
+            if constexpr (PK::first(k, A)) {
+                const pv2 tp = {pbcc<ii>(t), pbcc<ii - 1>(t)};
+                pv2 mp = {Mc[ii], Mc[ii - 1]};
+                mp = __builtin_elementwise_fma(-tp, mk2, mp);
+                Mc[ii] = mp.x;
+                Mc[ii - 1] = mp.y;
+            } else if constexpr (!PK::second(k, A)) {
+                Mc[ii] -= pbcc<ii>(t) * Mc[k];
+            }
         });
         Mc[k] = t;
         dvec = ln == k ? inv : dvec;
@@ -137,7 +152,6 @@ constexpr int kWideScratchRows = 64 - MI_PAIR_WIDE_AREG;
 #ifndef MI_PAIR_JREUSE_MAXNV
 #define MI_PAIR_JREUSE_MAXNV 16   // narrow PGS reuses P9's J rows for models with nv <= this
 #endif
-typedef float pv2 __attribute__((ext_vector_type(2)));
 // J_r . u over the NV DOFs (u in LDS, uniform per half), in DOF order: the narrow and the wide
 // PGS form v_r the same way
 template <int NV, int NVC>

@@ -409,6 +409,79 @@ constexpr int ct_max_anc() {
     return m;
 }
 
+// Packed pairs of the tree updates. A pivot of the paired LTDL (mi_pair.hpp ct_ltdl_pair) updates
+// every ancestor j of its DOF with one FMA, the targets separate and one operand common: two of
+// them are one v_pk_fma_f32 (the same fused multiply-add per element, bit-identical, half the
+// VALU instructions). Paired are the ancestors 2m + 1 and 2m where both are on the list; lists
+// run nearest ancestor first, so that is positions A and A + 1 with parent(2m + 1) = 2m. The
+// register pair holds (2m + 1, 2m), the list's order.
+// pair[i] bit A: positions A, A + 1 of DOF i's list are one packed update; the rest stay scalar.
+// (The first pass of ct_solve_l has the same shape, and packed by this table it made the Humanoid
+// pair kernels spill VGPRs: DESIGN.md section 2.)
+template <int NV>
+struct CtPk {
+    unsigned pair[NV > 0 ? NV : 1];
+    int npairs;
+};
+template <class T>
+constexpr CtPk<T::nv> ct_pk_make() {
+    CtPk<T::nv> p{};
+    for (int i = 0; i < T::nv; ++i) {
+        const int a0 = T::dof.anc_start[i], na = T::dof.anc_start[i + 1] - a0;
+        for (int A = 0; A < na;) {
+            const int j = T::dof.anc[a0 + A];
+            if ((j & 1) && A + 1 < na && T::dof.anc[a0 + A + 1] == j - 1) {
+                p.pair[i] |= 1u << A;
+                ++p.npairs;
+                A += 2;
+            } else {
+                ++A;
+            }
+        }
+    }
+    return p;
+}
+// every DOF's packed pairs and leftovers together are exactly its ancestor list, each entry once,
+// and a pair's targets are the registers (2m + 1, 2m) with adjacent factor entries
+template <class T>
+constexpr bool ct_pk_exact(const CtPk<T::nv>& p) {
+    for (int i = 0; i < T::nv; ++i) {
+        const int a0 = T::dof.anc_start[i], na = T::dof.anc_start[i + 1] - a0;
+        unsigned seen = 0u;      // DOFs updated, by the pairs and by the leftovers
+        int updates = 0;
+        if (na < 32 && (p.pair[i] >> na)) return false;
+        for (int A = 0; A < na; ++A) {
+            const bool second = A > 0 && ((p.pair[i] >> (A - 1)) & 1u);
+            if ((p.pair[i] >> A) & 1u) {
+                if (second || A + 1 >= na) return false;   // overlapping pairs, or one past the list
+                const int j = T::dof.anc[a0 + A], j2 = T::dof.anc[a0 + A + 1];
+                if (!(j & 1) || j2 != j - 1) return false;
+                if ((seen >> j) & 1u || (seen >> j2) & 1u) return false;
+                seen |= (1u << j) | (1u << j2);
+                updates += 2;
+            } else if (!second) {
+                const int j = T::dof.anc[a0 + A];
+                if ((seen >> j) & 1u) return false;
+                seen |= 1u << j;
+                ++updates;
+            }
+        }
+        if (seen != T::dof.anc_mask[i] || updates != na) return false;
+    }
+    return true;
+}
+template <class T>
+struct CtPkTab {
+    static constexpr CtPk<T::nv> pk = ct_pk_make<T>();
+    static_assert(ct_pk_exact<T>(pk), "packed and leftover updates must be each DOF's ancestor list, each entry once");
+    static constexpr bool first(int i, int A) { return (pk.pair[i] >> A) & 1u; }
+    static constexpr bool second(int i, int A) { return A > 0 && ((pk.pair[i] >> (A - 1)) & 1u); }
+};
+// two floats in an aligned register pair: the operands of the packed FP32 instructions
+// (v_pk_fma_f32, v_pk_mul_f32, v_pk_add_f32), here and in mi_pair.hpp
+typedef float pv2 __attribute__((ext_vector_type(2)));
+typedef pv2 pv2_a4 __attribute__((aligned(4)));   // two adjacent floats at any word (LDS: one ds_read2_b32)
+
 // The step fences keep each step's FMAs in order (and the factor loads from being front-loaded
 // into hundreds of live registers), which also kept every step's LDS broadcast reads behind
 // the previous step: one LDS round trip exposed per step, 2 nv per solve. The factor entries
@@ -454,11 +527,23 @@ MI_D void ct_solve_l(const float* Lr, float (&x)[T::nvc], float& a) {
         constexpr int i = (int)S;
         if constexpr (i < T::nv) load(std::integral_constant<int, i>{}, std::integral_constant<int, i % NB>{});
     });
-    sfor<0, T::nv>([&](auto I) {
-        const float y = x[I];
-        x[I] = y * Lr[T::dof.lrow[T::nv] + I];
-        a += y * x[I];
+    // D^-1: two DOFs per v_pk_mul_f32 (the same product per element, the two 1/D from one
+    // two-word broadcast read); the sum keeps its order
+    sfor<0, T::nv / 2>([&](auto M) {
+        constexpr int m = M;
+        const float y0 = x[2 * m], y1 = x[2 * m + 1];
+        const pv2 d = *(const pv2_a4*)(Lr + T::dof.lrow[T::nv] + 2 * m);
+        const pv2 xp = pv2{y1, y0} * pv2{d.y, d.x};
+        x[2 * m + 1] = xp.x;
+        x[2 * m] = xp.y;
+        a += y0 * x[2 * m];
+        a += y1 * x[2 * m + 1];
     });
+    if constexpr (T::nv & 1) {
+        const float y = x[T::nv - 1];
+        x[T::nv - 1] = y * Lr[T::dof.lrow[T::nv] + T::nv - 1];
+        a += y * x[T::nv - 1];
+    }
     sfor<0, T::nv>([&](auto I) {                      // x <- L^-1 x (root -> leaves)
         constexpr int i = I;
         constexpr int a0 = T::dof.anc_start[i], na = T::dof.anc_start[i + 1] - a0;
