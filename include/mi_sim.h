@@ -273,7 +273,12 @@ int mi_solve_mass(mi_sim* sim, int32_t which, const float* rhs, int32_t R, float
  * B = joint damping (0 on root DOFs). With MI_MASS_STEPPER, u + dt*acc is the velocity one
  * contact-free, limit-free substep produces (mi_sim_params.angular_damping aside). While a body
  * wrench buffer exists (mi_apply_link_wrenches) its generalized force Q is part of the right-hand
- * side, as in the step: Mt^-1 (S^T tau + Q - c - g - B u); without one the result is unchanged. */
+ * side, as in the step: Mt^-1 (S^T tau + Q - c - g - B u); without one the result is unchanged.
+ * While joint drive records exist (mi_set_drive_gains) the three calls see the drive as the step does
+ * (include/mi_drive.h): MI_MASS_STEPPER's diagonal is armature + dt * B_E, B_E = (B + kd) + dt kp, and
+ * forward dynamics uses B_E u and adds F_d = kp (q* - q) + kd qd* to tau, so the sentence above on
+ * u + dt*acc stays true under a drive. MI_MASS_ARMATURE is continuous time: its matrix is unchanged
+ * (the same bits), its forward dynamics uses B + kd and adds F_d. Without records: unchanged bits. */
 int mi_get_forward_dynamics(mi_sim* sim, int32_t which, const float* tau, float* acc, void* stream);
 
 /* Frames as mi_get_link_jacobian (host link_ids[K], offsets[K,3]|NULL). Either output may be
@@ -305,6 +310,9 @@ enum { MI_MASS_RIGID = 2 };   /* M alone: inverse dynamics only (harmless to mul
  * so mi_get_forward_dynamics(which, tau[:,joint dofs]) returns acc when the root entries of tau are 0.
  * Root entries (floating base) are the wrench the world must apply at the root origin. acc = NULL
  * gives the bits an all-zero acc gives. MI_E_ARG for any other `which`.
+ * Joint drives (mi_set_drive_gains), like the body wrenches' Q, are NOT part of it: the call answers
+ * which efforts a motion needs, whatever supplies them (with a drive or a wrench in effect, forward
+ * dynamics of the returned tau is that motion plus what they add).
  * joint_wrench [N,L,6]|NULL: (force, torque about link l's origin), world axes, that link l's
  * parent (the world for link 0) transmits to link l for that motion under MI_MASS_RIGID terms
  * (inertial + velocity-product - gravity forces of l's subtree; no armature, no damping):
@@ -402,6 +410,45 @@ int mi_apply_link_wrenches(mi_sim* sim, const int32_t* link_ids, const float* of
 int mi_clear_link_wrenches(mi_sim* sim, const int64_t* idx, int32_t n, void* stream);
 /* Q [N,nv] device <- the generalized force in effect (zeros before any wrench was applied). */
 int mi_get_applied_generalized_forces(mi_sim* sim, float* Q, void* stream);
+/* --- implicit PD joint drives: ArticulationView.set_gains / set_joint_position_targets /
+ *     set_joint_velocity_targets (tasks/anymal.py:187, franka_cabinet.py:254,285, ball_balance.py:188,
+ *     quadcopter.py:158, shared/in_hand_manipulation.py:267,329) ---
+ * Per env and joint DOF a stiffness kp, a damping kd, a position target q* and a velocity target qd*.
+ * Every substep applies the joint torque tau_d = kp (q* - q+) + kd (qd* - u+) at its END state
+ * (q+ = q + dt u+), solved with the velocities: with
+ *     B_E = (B + kd) + dt kp        F_d = kp (q* - q) + kd qd*      (include/mi_drive.h)
+ * the substep solves (M + arm + dt B_E) (u+ - u) / dt = S^T (tau + F_d) + Q - c - g - B_E u, q the
+ * substep's own positions, so F_d follows the joint within one mi_sim_step(k) or mi_env_step, which
+ * an effort set from outside cannot. The contact and joint-limit rows see the drive's stiffness
+ * through that matrix. tau is the effort in force (mi_set_dof_efforts, or actions * gear in the
+ * fused env step): the drive adds to it. There is no effort cap (PhysX's maxForce) and the
+ * mask-driven reset keeps gains and targets: a task sets targets in its own reset.
+ * Storage: a sim-owned buffer of four lines of D floats per env (kp, kd, q*, qd*), absent until the
+ * first setter call; all zeros is no drive. kd is NOT written into the table's MI_ENVP_DAMPING slot:
+ * mi_set_env_params / mi_get_env_params and the physics DR schedules keep their meaning, and B above
+ * is that slot. The first setter call allocates the buffer (zeros) and, if absent, the per-env
+ * parameter table with the nominal values: only the kernel variants that read the table read the
+ * drive, and the plain kernels know nothing of it. Hence the table's limits: MI_E_STATE on the
+ * wavefront-per-env path and for a first call inside a stream capture; MI_E_ARG for
+ * MI_DYN_CARTPOLE. mi_sim_clear_env_params drops the buffer with the table.
+ * kp, kd / q_target, qd_target: DEVICE [n,D], either may be NULL (that line keeps its values), not
+ * both (MI_E_NULL); idx: device int64 [n]|NULL (rows 0..n-1; out-of-range ids are ignored; an id
+ * named twice in one call is undefined). MI_E_SHAPE for n < 0 (n > N without idx). The values are
+ * stored as given: negative or non-finite gains, and targets outside the joint limits, are the
+ * caller's responsibility.
+ * Like the other entry points the calls issue deferred substeps first (those ran under the drive of
+ * their request), are stream-ordered, do not block the host and allocate nothing after the first use
+ * (capturable). They do not write the state: the mirrors stay valid. */
+int mi_set_drive_gains(mi_sim* sim, const float* kp, const float* kd, const int64_t* idx, int32_t n,
+                       void* stream);
+int mi_set_drive_targets(mi_sim* sim, const float* q_target, const float* qd_target, const int64_t* idx,
+                         int32_t n, void* stream);
+/* Each [N,D] device, any may be NULL: the values in effect, the bits that were set (zeros before any
+ * setter call). */
+int mi_get_drives(mi_sim* sim, float* kp, float* kd, float* q_target, float* qd_target, void* stream);
+/* All four lines of the envs named <- exact zeros (idx NULL, n = N: all): from the next substep on
+ * they step to the bits of a sim that never had a drive. A no-op before the first setter call. */
+int mi_clear_drives(mi_sim* sim, const int64_t* idx, int32_t n, void* stream);
 /* State mirrors: row-major copies of the articulation state in caller-owned device buffers, the
  * tensors ArticulationView getters hand out with clone=False (get_world_poses, get_velocities,
  * get_joint_positions / velocities, _physics_view.get_force_sensor_forces: locomotion.py:81-89;
@@ -542,8 +589,9 @@ int mi_set_env_params(mi_sim* sim, int32_t attr, const float* values /*[n,dim] d
 int mi_get_env_params(mi_sim* sim, int32_t attr, float* out /*[N,dim] device*/, void* stream);
 /* Drops the table (and leaves the physics DR schedules off): back to the nominal physics and to
  * the kernels that know no table. The body wrench buffer (mi_apply_link_wrenches) rides on the
- * table's kernels and is dropped with it: no generalized force is in effect afterwards. Waits for
- * the device. */
+ * table's kernels and is dropped with it: no generalized force is in effect afterwards. So are
+ * the joint drive records (mi_set_drive_gains): no drive is in effect afterwards. Waits for the
+ * device. */
 int mi_sim_clear_env_params(mi_sim* sim);
 
 /* Physics DR schedules (include/mi_dr_phys.h): per attribute an optional on_reset and an optional

@@ -110,10 +110,13 @@ MI_D void make_row(const DevModel& m, const WS& w, int r, int l, const float* f)
 // kEnvP: joint damping / armature from env i's record ep of the per-env parameter table
 // (include/mi_sim.h mi_set_env_params; layout: mi_topo.hpp); the caller passes the record's
 // gravity and friction in p. wq (kEnvP only, may be null): the body wrenches' generalized forces
-// [N][nv] (mi_wrench.hpp), added to every DOF's right-hand side; null: no add at all.
+// [N][nv] (mi_wrench.hpp), added to every DOF's right-hand side; null: no add at all. drv (kEnvP
+// only, may be null): the joint drives' records [N][4][D] (include/mi_drive.h), which turn a joint
+// DOF's damping and effort into mi_drive_damping / mi_drive_effort at the substep's own q.
 template <bool kEnvP = false>
 MI_D void artic_substep(const DevModel& m, const DevState& st, const SimP& p, int i,
-                        const float* ep = nullptr, const float* wq = nullptr) {
+                        const float* ep = nullptr, const float* wq = nullptr,
+                        const float* drv = nullptr) {
     const int N = st.N, L = m.L, D = m.D, nv = m.nv, nr = m.nr;
     const float dt = p.dt;
     WS w(st.ws, m.slots, i);
@@ -264,9 +267,16 @@ MI_D void artic_substep(const DevModel& m, const DevState& st, const SimP& p, in
         float rhs = -Ck;
         if (k >= nr) {
             if constexpr (kEnvP) {
-                const float damp = ep[4 + l - 1], arm = ep[4 + D + l - 1];
+                float damp = ep[4 + l - 1], eff = st.eff[sx(st, k - nr, i)];
+                const float arm = ep[4 + D + l - 1];
+                if (drv) {
+                    const float* dl = drv + (size_t)i * MI_DRIVE_LINES * D + (k - nr);
+                    const float kp = dl[MI_DRIVE_KP * D], kd = dl[MI_DRIVE_KD * D];
+                    eff = mi_drive_effort(eff, kp, kd, st.q[sx(st, k - nr, i)], dl[MI_DRIVE_QT * D], dl[MI_DRIVE_QDT * D]);
+                    damp = mi_drive_damping(damp, kp, kd, dt);
+                }
                 diag += arm + dt * damp;
-                rhs += st.eff[sx(st, k - nr, i)] - damp * w[m.o_u + k];
+                rhs += eff - damp * w[m.o_u + k];
             } else {
                 diag += m.armature[l] + dt * m.damping[l];
                 rhs += st.eff[sx(st, k - nr, i)] - m.damping[l] * w[m.o_u + k];

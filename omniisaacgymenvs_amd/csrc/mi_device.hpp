@@ -14,6 +14,7 @@
 #include "../../include/mi_sim.h"
 #include "../../include/mi_dr.h"
 #include "../../include/mi_dr_phys.h"
+#include "../../include/mi_drive.h"
 
 #define MI_D __device__ __forceinline__
 #define MI_MAXA 32     // max actions / joint DOFs handled by the task kernels

@@ -46,6 +46,9 @@ struct MsArgs {
     float* out;               // MS_SOLVE: out; MS_FD: acc; MS_TASK: minv_jt or nullptr
     float* lam;               // MS_TASK: lam_inv or nullptr
     const float* wq;          // MS_FD: the body wrenches' generalized forces [N,nv] (mi_wrench.hpp) or nullptr
+    const float* drv;         // the joint drives' records [N][4][D] (include/mi_drive.h) or nullptr: MI_MASS_STEPPER's
+                              // diagonal takes dt * mi_drive_damping; MS_FD its damping (kd alone in
+                              // MI_MASS_ARMATURE, continuous time) and mi_drive_effort
 };
 
 // LDS. Masks, the double inertias of the M path, cor / grav, state, ancestor lists (bytes), DOF axes
@@ -471,8 +474,12 @@ __global__ __launch_bounds__(kLinkThreads) void k_mass_solve(DevModel m, DevStat
         if (r == c && r >= nr) {
             const int j = r - nr;
             const float* rec = gv.envp ? gv.envp + (size_t)(e0 + e) * gv.stride : nullptr;
-            const float damp = rec ? rec[kEnvpDamping + j] : m.damping[j + 1];
+            float damp = rec ? rec[kEnvpDamping + j] : m.damping[j + 1];
             const float arm = rec ? rec[kEnvpDamping + D + j] : m.armature[j + 1];
+            if (a.drv && a.which == MI_MASS_STEPPER) {
+                const float* dl = a.drv + (size_t)(e0 + e) * MI_DRIVE_LINES * D + j;
+                damp = mi_drive_damping(damp, dl[MI_DRIVE_KP * D], dl[MI_DRIVE_KD * D], a.dt);
+            }
             v += a.which == MI_MASS_STEPPER ? arm + a.dt * damp : arm;
         }
         Hb[e * MB + r * ms + c] = v;
@@ -515,8 +522,15 @@ __global__ __launch_bounds__(kLinkThreads) void k_mass_solve(DevModel m, DevStat
                 val = -scor[e * nv + c] - sgrav[e * nv + c];
                 if (c >= nr) {
                     const int j = c - nr;
-                    const float damp = gv.envp ? gv.envp[(size_t)(e0 + e) * gv.stride + kEnvpDamping + j] : m.damping[j + 1];
-                    const float tau = a.rhs ? a.rhs[(size_t)(e0 + e) * D + j] : st.eff[sx(st, j, e0 + e)];
+                    float damp = gv.envp ? gv.envp[(size_t)(e0 + e) * gv.stride + kEnvpDamping + j] : m.damping[j + 1];
+                    float tau = a.rhs ? a.rhs[(size_t)(e0 + e) * D + j] : st.eff[sx(st, j, e0 + e)];
+                    if (a.drv) {
+                        // the stepper's B_E and tau + F_d; in continuous time the spring is all force
+                        const float* dl = a.drv + (size_t)(e0 + e) * MI_DRIVE_LINES * D + j;
+                        const float kp = dl[MI_DRIVE_KP * D], kd = dl[MI_DRIVE_KD * D];
+                        tau = mi_drive_effort(tau, kp, kd, se[e * SW + kLinkRootW + j], dl[MI_DRIVE_QT * D], dl[MI_DRIVE_QDT * D]);
+                        damp = mi_drive_damping(damp, a.which == MI_MASS_STEPPER ? kp : 0.0f, kd, a.dt);
+                    }
                     val += tau - damp * se[e * SW + kLinkRootW + D + j];
                 }
                 if (a.wq) val += a.wq[(size_t)(e0 + e) * nv + c];

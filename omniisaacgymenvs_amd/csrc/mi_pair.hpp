@@ -360,13 +360,16 @@ template <class TP>
 MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevState& st,
                              const SimP& p, int i, int wv_, const float* mcb, float* sm, float* gW_,
                              bool load_state, bool store_state, int& prio, int& load,
-                             const float* ep = nullptr, const float* wq = nullptr) {
+                             const float* ep = nullptr, const float* wq = nullptr,
+                             const float* drv = nullptr) {
     const glb_f gW = glb_ptr(gW_);   // every slab access below is a global op, not a flat one
     // ep (TP::kEnvP only): env i's record of the per-env parameter table. LDS and registers are
     // both full here (Humanoid: 432 B of LDS spare per workgroup, 2 waves / SIMD), so the record
     // is not kept across the substep: its lines are read where the state's effort line is (P3:
     // lane = DOF, coalesced), gravity at P1 and friction once ahead of the PGS sweeps
     // wq (TP::kEnvP only, may be null): the body wrenches' generalized forces [N][nv], read at P3
+    // drv (TP::kEnvP only, may be null): the joint drives' records [N][4][D] (include/mi_drive.h), read at
+    // P3 too and not staged in LDS: four loads per joint DOF, combined and dead before the CRBA rows
     static_assert(TP::kCT && TP::nv <= 32, "paired kernel: compiled topology, nv <= 32");
     const int lane = pair_l64() & 31;
     const int L = m.L, D = m.D, nv = m.nv, nr = m.nr;
@@ -405,7 +408,7 @@ MI_D void pair_artic_substep(const DevModel& m, const WaveTabs& t, const DevStat
     wave_sync();
     STAMP(2);
     // ---- P3: bias + CRBA rows (lane = DOF), shared with the one-env-per-wave kernel
-    phase_p3_bias_crba<Grp32, TP>(lane, i, D, nv, nr, dt, us, rhs, Mx, Ss, mc, t, st, aux, ep, wq);
+    phase_p3_bias_crba<Grp32, TP>(lane, i, D, nv, nr, dt, us, rhs, Mx, Ss, mc, t, st, aux, ep, wq, drv, sm + t.s_q);
     wave_sync();
     STAMP(3);
     // ---- P4: register LTDL (lane = column), factor published to LDS

@@ -76,11 +76,16 @@ constexpr int sdof_first_loaded(int nr) { return nr == 6 ? 6 : 0; }
 // wq (TP::kEnvP only, may be null): the body wrenches' generalized forces [N][nv]
 // (mi_wrench.hpp), env i's line read the same way and added to every DOF's bias, the root's
 // included; null (no wrench was ever applied): no add at all
+// drv (TP::kEnvP only, may be null): the joint drives' records [N][4][D] (include/mi_drive.h: lines
+// kp, kd, q*, qd*, lane = DOF like the effort line) and qs, the substep's own joint positions in
+// LDS: damping and effort of a joint DOF become mi_drive_damping / mi_drive_effort. The four values
+// are combined at once and dead before the CRBA rows; null (no drive call yet): no read at all
 template <class G, class TP>
 MI_D void phase_p3_bias_crba(int lane, int i, int D, int nv, int nr, float dt, const float* us, float* rhs,
                              float* Mx, const float* Ss, const MC& mc, const WaveTabs& t,
                              const DevState& st, const float* aux, const float* ep,
-                             const float* wq = nullptr) {
+                             const float* wq = nullptr, const float* drv = nullptr,
+                             const float* qs = nullptr) {
     if (lane < nv) {
         const int k = lane, l = k < nr ? 0 : k - nr + 1;
         float s[6], I[10], f[6], F[6];
@@ -106,8 +111,17 @@ MI_D void phase_p3_bias_crba(int lane, int i, int D, int nv, int nr, float dt, c
                 damp = mc.lf(MC_DAMP, l);
                 arm = mc.lf(MC_ARM, l);
             }
+            float eff = st.eff[sx(st, k - nr, i)];
+            if constexpr (TP::kEnvP) {
+                if (drv) {
+                    const float* dl = drv + (size_t)i * MI_DRIVE_LINES * D + (k - nr);
+                    const float kp = dl[MI_DRIVE_KP * D], kd = dl[MI_DRIVE_KD * D];
+                    eff = mi_drive_effort(eff, kp, kd, qs[k - nr], dl[MI_DRIVE_QT * D], dl[MI_DRIVE_QDT * D]);
+                    damp = mi_drive_damping(damp, kp, kd, dt);
+                }
+            }
             diag += arm + dt * damp;
-            r += st.eff[sx(st, k - nr, i)] - damp * us[k];
+            r += eff - damp * us[k];
         }
         if constexpr (TP::kEnvP) {
             if (wq) r += wq[(size_t)i * nv + k];

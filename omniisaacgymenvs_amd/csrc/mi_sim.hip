@@ -110,6 +110,10 @@ struct mi_sim {
     // body wrenches (mi_apply_link_wrenches): their generalized forces [N][nv], added to the bias by
     // the EnvP / *_envp kernels; nullptr until the first wrench (and again after the table is dropped)
     float* wq = nullptr;
+    // joint drives (mi_set_drive_gains / mi_set_drive_targets): per env four lines of D floats, kp, kd,
+    // q*, qd* (include/mi_drive.h), read by the same kernels; nullptr until the first drive call (and
+    // again after the table is dropped); all zeros = no drive
+    float* drv = nullptr;
     std::vector<float> nominal;       // the sim-wide values in record order [4 + 2 D]
     const float* nominal_dev = nullptr;
     // physics DR schedules (mi_sim_set_phys_dr): descriptor + per-component distribution
@@ -167,7 +171,7 @@ static void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipS
 template <bool kEnvP = false>
 __device__ __forceinline__ void physics_env(const DevModel& m, const DevState& st, const SimP& p,
                                             int i, int substeps, const float* ep = nullptr,
-                                            const float* wq = nullptr) {
+                                            const float* wq = nullptr, const float* drv = nullptr) {
     if constexpr (kEnvP) {
         // the record's scalars once per launch, in registers: the substeps see them as the sim's
         SimP pe = p;
@@ -179,7 +183,7 @@ __device__ __forceinline__ void physics_env(const DevModel& m, const DevState& s
             me.pole_damping = ep[kEnvpDamping + 1];
             physics_env<false>(me, st, pe, i, substeps);
         } else {
-            for (int s = 0; s < substeps; ++s) artic_substep<true>(m, st, pe, i, ep, wq);
+            for (int s = 0; s < substeps; ++s) artic_substep<true>(m, st, pe, i, ep, wq, drv);
         }
         return;
     }
@@ -201,10 +205,10 @@ __global__ void k_sim_step(DevModel m, DevState st, SimP p, int substeps) {
     physics_env(m, st, p, i, substeps);
 }
 __global__ void k_sim_step_envp(DevModel m, DevState st, SimP p, int substeps, const float* envp,
-                                int envp_stride, const float* wq) {
+                                int envp_stride, const float* wq, const float* drv) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= st.N) return;
-    physics_env<true>(m, st, p, i, substeps, envp + (size_t)i * envp_stride, wq);
+    physics_env<true>(m, st, p, i, substeps, envp + (size_t)i * envp_stride, wq, drv);
 }
 
 __global__ void k_pre_step(DevModel m, DevState st, DevTask tp, const float* actions,
@@ -426,11 +430,11 @@ __global__ void k_env_step_envp(DevModel m, DevState st, SimP p, DevTask tp, con
                                 int substeps, float* obs_out, float* obs_task, float* rew,
                                 int64_t* reset_buf, int64_t* progress_buf, float* pot, float* prev,
                                 float* actions_out, float* rew_out, int64_t* reset_out,
-                                const float* envp, int envp_stride, const float* wq) {
+                                const float* envp, int envp_stride, const float* wq, const float* drv) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= st.N) return;
     task_pre_env(m, st, tp, i, actions, reset_buf, progress_buf, pot, prev, actions_out, true);
-    physics_env<true>(m, st, p, i, substeps, envp + (size_t)i * envp_stride, wq);
+    physics_env<true>(m, st, p, i, substeps, envp + (size_t)i * envp_stride, wq, drv);
     MI_ENV_STEP_POST();
 }
 
@@ -450,6 +454,7 @@ struct KParams {
     const float* envp;
     int envp_stride;
     const float* wq;   // body wrenches' generalized forces [N][nv] or nullptr (EnvP instantiations only)
+    const float* drv;  // joint drives' records [N][4][D] or nullptr (EnvP instantiations only)
 };
 
 // launch with the model's compile-time topology (mi_topo_gen.hpp) or the runtime tables
@@ -493,7 +498,7 @@ static int sync_kparams(mi_sim* s) {
     if (!s->wave) return MI_OK;
     KParams h{};
     h.m = s->dm; h.t = s->wt; h.st = s->ds; h.p = s->sp; h.tp = s->tp; h.rows = s->rows;
-    h.envp = s->envp; h.envp_stride = s->envp_stride; h.wq = s->wq;
+    h.envp = s->envp; h.envp_stride = s->envp_stride; h.wq = s->wq; h.drv = s->drv;
     if (!s->kp_dev) {
         void* p = nullptr;
         int rc = dev_alloc(s, &p, sizeof(KParams));
@@ -889,10 +894,11 @@ __global__ __launch_bounds__(512) MI_PAIR_OCC void k_sim_step_pair(const KParams
     for (int s = 0; s < substeps; ++s) {
         const KParams* k = opaque_kp(kp);
         const float* ep = nullptr;         // env i's parameter record (the env the wave simulates,
-        const float* wq = nullptr;         // not its workgroup slot) and the body wrenches' forces
-        if constexpr (T::kEnvP) { ep = k->envp + (size_t)i * k->envp_stride; wq = k->wq; }
+        const float* wq = nullptr;         // not its workgroup slot), the body wrenches' forces
+        const float* drv = nullptr;        // and the joint drives' records
+        if constexpr (T::kEnvP) { ep = k->envp + (size_t)i * k->envp_stride; wq = k->wq; drv = k->drv; }
         pair_artic_substep<T>(k->m, k->t, k->st, k->p, i, pair_wave(), smem, sm, gW, s == 0, s == substeps - 1,
-                              prio, load, ep, wq);
+                              prio, load, ep, wq, drv);
     }
     // World.step() then the getters (locomotion.py:81-89): the final state is still in LDS, so the
     // launch writes the getters' row-major mirrors itself (the same values it stored to the
@@ -945,10 +951,11 @@ __global__ __launch_bounds__(512) MI_PAIR_OCC void k_env_step_pair(const KParams
     for (int s = 0; s < substeps; ++s) {
         const KParams* k = opaque_kp(kp);
         const float* ep = nullptr;         // env i's parameter record (the env the wave simulates,
-        const float* wq = nullptr;         // not its workgroup slot) and the body wrenches' forces
-        if constexpr (T::kEnvP) { ep = k->envp + (size_t)i * k->envp_stride; wq = k->wq; }
+        const float* wq = nullptr;         // not its workgroup slot), the body wrenches' forces
+        const float* drv = nullptr;        // and the joint drives' records
+        if constexpr (T::kEnvP) { ep = k->envp + (size_t)i * k->envp_stride; wq = k->wq; drv = k->drv; }
         pair_artic_substep<T>(k->m, k->t, k->st, k->p, i, pair_wave(), smem, sm, gW, s == 0, s == substeps - 1,
-                              prio, load, ep, wq);
+                              prio, load, ep, wq, drv);
     }
     STAMP_RESET();
     pair_loco_post(m, t, st, tp, i, sm, a_lane, obs_out, obs_task, rew, reset_buf, progress_buf,
@@ -1155,6 +1162,38 @@ __global__ __launch_bounds__(256) void k_envp_get(const float* __restrict__ envp
     if (t >= (int64_t)N * dim) return;
     const int i = (int)(t / dim), c = (int)(t - (int64_t)i * dim);
     out[t] = envp ? envp[(size_t)i * stride + base + c] : nominal[base + c];
+}
+
+// ---- joint drive records (include/mi_sim.h mi_set_drive_gains; lines: include/mi_drive.h) ----
+// rows [n, D] of up to two neighbouring lines (line, line + 1) -> the records of envs idx[r] (or r);
+// a null row pointer leaves its line alone; zero: all four lines <- exact zeros instead.
+// Out-of-range ids are ignored.
+struct DriveRows { const float* v[2]; };
+__global__ __launch_bounds__(256) void k_drive_set(float* __restrict__ drv, int D, int line, DriveRows rows,
+                                                   bool zero, const int64_t* __restrict__ idx, int n, int N) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)n * D) return;
+    const int r = (int)(t / D), c = (int)(t - (int64_t)r * D);
+    const int64_t i = idx ? idx[r] : (int64_t)r;
+    if (i < 0 || i >= N) return;
+    float* rec = drv + (size_t)i * MI_DRIVE_LINES * D + c;
+    if (zero) {
+#pragma unroll
+        for (int l = 0; l < MI_DRIVE_LINES; ++l) rec[l * D] = 0.0f;
+        return;
+    }
+    if (rows.v[0]) rec[line * D] = rows.v[0][t];
+    if (rows.v[1]) rec[(line + 1) * D] = rows.v[1][t];
+}
+// the four lines of every env -> [N, D] each (a null output is skipped; drv == nullptr: zeros)
+struct DriveOut { float* v[MI_DRIVE_LINES]; };
+__global__ __launch_bounds__(256) void k_drive_get(const float* __restrict__ drv, int D, DriveOut out, int N) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)N * D) return;
+    const int i = (int)(t / D), c = (int)(t - (int64_t)i * D);
+#pragma unroll
+    for (int l = 0; l < MI_DRIVE_LINES; ++l)
+        if (out.v[l]) out.v[l][t] = drv ? drv[((size_t)i * MI_DRIVE_LINES + l) * D + c] : 0.0f;
 }
 
 // ---- physics DR schedule kernel (include/mi_dr_phys.h) -----------------------------------
@@ -2053,7 +2092,7 @@ static int launch_sim(mi_sim* s, int substeps, hipStream_t stream) {
             launch(V.sim, wave_grid(s), wave_block(s), s->lds_bytes, stream, nullptr, nullptr, kp, substeps);
         } else if constexpr (decltype(V)::kEnvP) {
             launch(V.sim, grid_for(s, s->N), dim3(s->block), 0, stream, nullptr, nullptr, s->dm, s->ds, s->sp,
-                   substeps, s->envp, s->envp_stride, s->wq);
+                   substeps, s->envp, s->envp_stride, s->wq, s->drv);
         } else {
             launch(V.sim, grid_for(s, s->N), dim3(s->block), 0, stream, nullptr, nullptr, s->dm, s->ds, s->sp,
                    substeps);
@@ -2231,6 +2270,7 @@ static int mass_solve_launch(mi_sim* s, const char* fn, int32_t which, int op, c
     a.dt = s->sp.dt;
     a.rhs = rhs; a.out = out; a.lam = lam;
     a.wq = op == MS_FD ? s->wq : nullptr;
+    a.drv = s->drv;
     const size_t lds = MsLds(s->dm.L, s->dm.D, s->dm.nv, K, a.VT).bytes();
     if (lds > kMsLdsLimit) return fail(MI_E_SHAPE, "%s: %zu B of LDS per workgroup", fn, lds);
     static const LinkReq none{};
@@ -2743,7 +2783,7 @@ int mi_env_step(mi_sim* s, const float* actions, int32_t substeps, float* obs_ou
         else if constexpr (decltype(V)::kEnvP)
             launch(V.env, grid_for(s, s->N), dim3(s->block), 0, STREAM(stream), ev0, ev1, s->dm, s->ds, s->sp,
                    s->tp, actions, substeps, obs_out, obs_task, rew, reset_buf, progress_buf, potentials,
-                   prev_potentials, actions_out, rew_out, reset_out, s->envp, s->envp_stride, s->wq);
+                   prev_potentials, actions_out, rew_out, reset_out, s->envp, s->envp_stride, s->wq, s->drv);
         else
             launch(V.env, grid_for(s, s->N), dim3(s->block), 0, STREAM(stream), ev0, ev1, s->dm, s->ds, s->sp,
                    s->tp, actions, substeps, obs_out, obs_task, rew, reset_buf, progress_buf, potentials,
@@ -2923,6 +2963,8 @@ int mi_sim_clear_env_params(mi_sim* s) {
     s->envp_stride = 0;
     free_tracked(s, s->wq);   // the body wrenches ride on the table's kernels
     s->wq = nullptr;
+    free_tracked(s, s->drv);  // and so do the joint drives
+    s->drv = nullptr;
     return sync_kparams(s);
 }
 
@@ -2983,6 +3025,78 @@ int mi_get_applied_generalized_forces(mi_sim* s, float* Q, void* stream) {
     if (bytes == 0) return MI_OK;
     if (s->wq) HIP_TRY(hipMemcpyAsync(Q, s->wq, bytes, hipMemcpyDeviceToDevice, STREAM(stream)));
     else HIP_TRY(hipMemsetAsync(Q, 0, bytes, STREAM(stream)));
+    return MI_OK;
+}
+
+// ---- joint drives (include/mi_drive.h) -----------------------------------------------------
+// The drive records on first use, and the parameter table their kernels need.
+static int drive_ensure(mi_sim* s, hipStream_t stream, const char* fn) {
+    if (s->dm.dyn == MI_DYN_CARTPOLE)
+        return fail(MI_E_ARG, "%s: the analytic cart-pole takes joint efforts only (no joint drives)", fn);
+    if (int rc = envp_ensure(s, stream, fn)) return rc;
+    if (s->drv) return MI_OK;
+    if (capturing(stream)) return fail(MI_E_STATE, "%s: the first call allocates the drive records: make it before the capture", fn);
+    void* p = nullptr;
+    if (int rc = dev_alloc(s, &p, sizeof(float) * (size_t)s->N * MI_DRIVE_LINES * (size_t)std::max(1, s->dm.D))) return rc;   // zeros
+    HIP_TRY(hipDeviceSynchronize());   // first use only: the zeros are in place on every stream
+    s->drv = (float*)p;
+    return sync_kparams(s);
+}
+
+static int drive_set(mi_sim* s, const char* fn, int line, const float* a, const float* b, const int64_t* idx,
+                     int32_t n, void* stream) {
+    if (s->dm.dyn == MI_DYN_CARTPOLE)
+        return fail(MI_E_ARG, "%s: the analytic cart-pole takes joint efforts only (no joint drives)", fn);
+    if (n < 0 || (!idx && n > s->N)) return fail(MI_E_SHAPE, "%s: n %d out of range", fn, n);
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);      // deferred substeps ran under the drive of their request
+    if (int rc = drive_ensure(s, STREAM(stream), fn)) return rc;
+    if (n == 0 || s->dm.D == 0) return MI_OK;
+    DriveRows rows{{a, b}};
+    hipLaunchKernelGGL(k_drive_set, dim3((unsigned)(((int64_t)n * s->dm.D + 255) / 256)), dim3(256), 0, STREAM(stream),
+                       s->drv, s->dm.D, line, rows, false, idx, n, s->N);
+    LAUNCH_CHECK();
+    return MI_OK;
+}
+
+int mi_set_drive_gains(mi_sim* s, const float* kp, const float* kd, const int64_t* idx, int32_t n, void* stream) {
+    NEED(s);
+    if (!kp && !kd) return fail(MI_E_NULL, "mi_set_drive_gains: kp and kd are both null");
+    return drive_set(s, __func__, MI_DRIVE_KP, kp, kd, idx, n, stream);
+}
+
+int mi_set_drive_targets(mi_sim* s, const float* q_target, const float* qd_target, const int64_t* idx, int32_t n,
+                         void* stream) {
+    NEED(s);
+    if (!q_target && !qd_target) return fail(MI_E_NULL, "mi_set_drive_targets: q_target and qd_target are both null");
+    return drive_set(s, __func__, MI_DRIVE_QT, q_target, qd_target, idx, n, stream);
+}
+
+int mi_get_drives(mi_sim* s, float* kp, float* kd, float* q_target, float* qd_target, void* stream) {
+    NEED(s);
+    if (s->dm.dyn == MI_DYN_CARTPOLE)
+        return fail(MI_E_ARG, "%s: the analytic cart-pole takes joint efforts only (no joint drives)", __func__);
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    if (s->dm.D == 0 || (!kp && !kd && !q_target && !qd_target)) return MI_OK;
+    DriveOut out{{kp, kd, q_target, qd_target}};
+    hipLaunchKernelGGL(k_drive_get, dim3((unsigned)(((int64_t)s->N * s->dm.D + 255) / 256)), dim3(256), 0, STREAM(stream),
+                       (const float*)s->drv, s->dm.D, out, s->N);
+    LAUNCH_CHECK();
+    return MI_OK;
+}
+
+int mi_clear_drives(mi_sim* s, const int64_t* idx, int32_t n, void* stream) {
+    NEED(s);
+    if (s->dm.dyn == MI_DYN_CARTPOLE)
+        return fail(MI_E_ARG, "%s: the analytic cart-pole takes joint efforts only (no joint drives)", __func__);
+    if (n < 0 || (!idx && n > s->N)) return fail(MI_E_SHAPE, "%s: n %d out of range", __func__, n);
+    HIP_TRY(hipSetDevice(s->device));
+    FLUSH(s, stream);
+    if (!s->drv || n == 0 || s->dm.D == 0) return MI_OK;
+    hipLaunchKernelGGL(k_drive_set, dim3((unsigned)(((int64_t)n * s->dm.D + 255) / 256)), dim3(256), 0, STREAM(stream),
+                       s->drv, s->dm.D, 0, DriveRows{}, true, idx, n, s->N);
+    LAUNCH_CHECK();
     return MI_OK;
 }
 

@@ -613,6 +613,69 @@ class ArticulationView:
         if rc:
             N.check(rc, "mi_clear_link_wrenches")
 
+    # ---- implicit PD joint drives (include/mi_sim.h mi_set_drive_gains, include/mi_drive.h): the
+    # reference's set_gains / set_joint_position_targets / set_joint_velocity_targets (anymal.py:187,
+    # franka_cabinet.py:254,285, ball_balance.py:188). Every substep applies
+    # kp (q* - q) + kd (qd* - qd) at its END state, solved with the velocities, on top of the efforts
+    # in force; no effort cap. Gains and targets stay until set again or cleared (a reset keeps
+    # them). kds are the drive's own: get / set_joint_dampings keep the passive damping. The first
+    # setter allocates the sim's buffers: make it before capturing a graph.
+    def _set_drive(self, fn_name: str, a, b, indices) -> None:
+        idx, n = self._idx(indices, torch.int64)      # i32 or i64 ids, as the other setters take
+        if n == 0:
+            return
+        rows = []
+        for v in (a, b):
+            v = None if v is None else self._f32(torch.as_tensor(v, device=self.device))
+            if v is not None and v.numel() != n * self.num_dof:       # the kernel trusts the shape
+                raise ValueError(f"{tuple(v.shape)} values for {n} envs x {self.num_dof} DOFs")
+            rows.append(v)
+        rc = getattr(self._lib, fn_name)(self.handle, N.ptr(rows[0]), N.ptr(rows[1]),
+                                         None if idx is None else idx.data_ptr(), n, self.stream())
+        if rc:
+            N.check(rc, fn_name)
+
+    def _get_drive(self, line: int, indices, clone: bool) -> torch.Tensor:
+        out = self._ms_buf(("drive", line), self.count, self.num_dof)
+        ptrs = [None] * 4
+        ptrs[line] = out.data_ptr()
+        rc = self._lib.mi_get_drives(self.handle, *ptrs, self.stream())
+        if rc:
+            N.check(rc, "mi_get_drives")
+        return self._out(out, None if indices is None else torch.as_tensor(indices, device=self.device), clone)
+
+    def set_gains(self, kps=None, kds=None, indices=None) -> None:
+        """Drive stiffness and damping [n, num_dof]; None keeps what is set."""
+        if kps is None and kds is None:
+            raise ValueError("set_gains: kps and kds are both None")
+        self._set_drive("mi_set_drive_gains", kps, kds, indices)
+
+    def get_gains(self, indices=None, clone: bool = True):
+        """(kps, kds), each [count, num_dof]: zeros before any was set."""
+        return self._get_drive(0, indices, clone), self._get_drive(1, indices, clone)
+
+    def set_joint_position_targets(self, positions, indices=None) -> None:
+        self._set_drive("mi_set_drive_targets", positions, None, indices)
+
+    def set_joint_velocity_targets(self, velocities, indices=None) -> None:
+        self._set_drive("mi_set_drive_targets", None, velocities, indices)
+
+    def get_joint_position_targets(self, indices=None, clone: bool = True) -> torch.Tensor:
+        return self._get_drive(2, indices, clone)
+
+    def get_joint_velocity_targets(self, indices=None, clone: bool = True) -> torch.Tensor:
+        return self._get_drive(3, indices, clone)
+
+    def clear_joint_drives(self, indices=None) -> None:
+        """Gains and targets of the envs ``indices`` (all by default) <- zeros: no drive from the next
+        substep on, and the same bits as a sim that never had one."""
+        idx, n = self._idx(indices, torch.int64)
+        if n == 0:
+            return
+        rc = self._lib.mi_clear_drives(self.handle, None if idx is None else idx.data_ptr(), n, self.stream())
+        if rc:
+            N.check(rc, "mi_clear_drives")
+
     # ---- per-env physics parameters (include/mi_sim.h mi_set_env_params) ----
     # The values omni.replicator.isaac's physics_view randomizes through the PhysX views
     # (randomize.py:308-430): gravity (SimulationContext), one friction coefficient per env
